@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: splat-pixel pairs blended per second, grouped cumprod forward + backward.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,11 +14,15 @@ kernels BASELINE.json's metric is quoted on.  Workload at every
 owns one cfg3-sized image band (1920x1080 pixels, mean 80 splats/pixel, heavy-tailed, M ~ 1.66e8
 pairs); pixel groups are independent so there is NO data-path collective (weak scaling).
 
-Beside the headline (outside its timed region) the line carries: `config.unclipped` (the same workload without the
+A plain run sets up, warms up (W steps), times exactly K steps and prints the headline; `ms_per_step` is one timed step.
+`--dump-outputs DIR` then also writes what the last timed step computed (see `dump_outputs`).
+
+With `--full`, beside the headline (outside its timed region) the line carries: `config.unclipped` (the same workload without the
 4096 clip of SURVEY.md §8d: the few pixels deeper than one tile's raw look-back window go through the scans' descriptor
 tree), `sharded_frames` (ONE cfg5 / cfg3 frame cut into N slices by sharding.partition_groups: strong scaling, with and
 without the frame gather + gradient scatter — BASELINE.json config 5), `function_level` (rows f1/f2, with the blend
-backward's issue roofline and lane use), `caller_level` (row f4).
+backward's issue roofline and lane use), `caller_level` (row f4), `cpu_baseline`, and `efficiency_vs_single_gpu` (every rank
+times its band alone for K steps first).
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the backward scan):
 algorithmic bytes (20 B x pairs per launch) / its mean duration measured with HIP events on the
@@ -612,6 +616,27 @@ def pmc_traffic(kernel, workload):
         return None
 
 
+DUMP_ENTRIES = 1 << 22  # entries per dumped array over all ranks: 2 arrays x 16 MiB of float32, within 64 MB in all
+
+
+def dump_outputs(directory, arrays, world=1):
+    """`--dump-outputs DIR`: write each float32 device tensor of `arrays` ({file name: tensor}) as DIR/<name>.npy.  A tensor
+    longer than DUMP_ENTRIES / world is written at a fixed sample of positions: sorted draws from a CPU generator seeded
+    with 0, the same for every run and every build with the same arguments (inputs are seeded too)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    keep = DUMP_ENTRIES // world
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > keep:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (keep,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a fresh child — `python -m torch.distributed.run
     --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port> bench.py <same arguments>`, the command
@@ -658,7 +683,12 @@ def main():
     ap.add_argument("--workload", default="cfg3",
                     help="cfg2 | cfg3 | cfg5band (one 8th of the 4K frame) | cfg3_unclipped (cfg3's run-length mix without the "
                          "clip at 4096 splats per pixel: a few pixels deeper than one scan tile)")
-    ap.add_argument("--cpu-sample", type=int, default=64_000_000, help="pairs in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=64_000_000, help="pairs in the CPU baseline sample of --full (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (forward y, backward dL/dx) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the single-GPU pass behind efficiency_vs_single_gpu, "
+                         "live-path pair, sharded frames, unclipped and cfg2 workloads, wrapper / function / caller level, CPU baseline")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -750,20 +780,25 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # every rank first times its own band ALONE (device synchronisation only, no barrier): the single-GPU rate that
-    # `efficiency_vs_single_gpu` is taken against — at N = 1 it is the headline itself
-    torch.cuda.synchronize()
-    ta = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    alone_rate = m * args.steps / (time.perf_counter() - ta)
+    alone_rate = 0.0
+    if args.full:
+        # every rank first times its own band ALONE (device synchronisation only, no barrier): the single-GPU rate that
+        # `efficiency_vs_single_gpu` is taken against — at N = 1 it is the headline itself
+        torch.cuda.synchronize()
+        ta = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        alone_rate = m * args.steps / (time.perf_counter() - ta)
     sync()
     t0 = time.perf_counter()
     for k in range(args.steps):
         step(ev[k])
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # before anything below writes into y / gin again
+        dump_outputs(args.dump_outputs, {("" if world == 1 else f"rank{rank}_") + "forward_y": y,
+                                         ("" if world == 1 else f"rank{rank}_") + "backward_grad_x": gin}, world)
 
     t_fwd = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps * 1e-3  # seconds per launch
     t_bwd = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps * 1e-3
@@ -776,11 +811,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         msum = stats[1:].clone()
         dist.all_reduce(msum, op=dist.ReduceOp.SUM)
-        dist.all_reduce(alone0, op=dist.ReduceOp.MAX)  # rank 0's figure, on every rank
+        if args.full:
+            dist.all_reduce(alone0, op=dist.ReduceOp.MAX)  # rank 0's figure, on every rank
         elapsed, total_pairs = float(tmax.item()), float(msum.item())
     else:
         total_pairs = float(m)
-    rank0_alone = float(alone0.item())
+    rank0_alone = float(alone0.item()) if args.full else None
 
     def headline():
         """The contract's fields: everything the timed region decided."""
@@ -793,8 +829,9 @@ def main():
             "per_gpu_pairs_per_s": total_pairs * args.steps / elapsed / world,
             "per_gpu_GBps": (BYTES_FWD + BYTES_BWD) * total_pairs * args.steps / elapsed / 1e9 / world,
             "per_gpu_frac_of_hbm_peak": (BYTES_FWD + BYTES_BWD) * total_pairs * args.steps / elapsed / 1e9 / world / HBM_PEAK_GBPS,
-            # aggregate rate / (N x the rate rank 0 reached on its own band before the first barrier); 1.0 at N = 1 up to timer noise
-            "efficiency_vs_single_gpu": total_pairs * args.steps / elapsed / (world * rank0_alone),
+            # aggregate rate / (N x the rate rank 0 reached on its own band before the first barrier); 1.0 at N = 1 up to timer
+            # noise; None without --full (no alone pass)
+            "efficiency_vs_single_gpu": None if rank0_alone is None else total_pairs * args.steps / elapsed / (world * rank0_alone),
             "rank0_alone_pairs_per_s": rank0_alone,
             "steps": args.steps,
             "warmup": args.warmup,
@@ -835,7 +872,16 @@ def main():
             },
         }
 
-    # Everything below is outside the timed region and optional.  With N > 1 it contains collectives; one that never
+    if not args.full:  # a plain run: the headline and nothing else
+        if rank == 0:
+            out = headline()
+            out["config"]["tiles_resolved_through_the_descriptor_tree"] = gc.last_lookback_tiles(dev)
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # Everything below is outside the timed region and runs with --full.  With N > 1 it contains collectives; one that never
     # returns (a rank lost, a fabric problem) must not cost the run its headline: after GCP_BENCH_EXTRAS_TIMEOUT seconds
     # (default 420) rank 0 prints the line it has and every rank leaves — with exit code 3, so that a hang shows in the
     # run's return code and not only in a field of the line.

@@ -23,6 +23,19 @@ def golden_world(z, name):
     return {k: torch.from_numpy(z[f"{name}/{k}"]) for k in ("mean", "variance_q", "variance_scale", "opacity", "color", "P", "K", "wh")}
 
 
+def _sh_condition_scale(w, c):
+    """Per Gaussian and channel, the sum of |term| of the degree-2 SH expansion that gives l_d in camera c (fp64, view
+    direction from the camera-space mean): the magnitude of the sum with every term taken in absolute value."""
+    mean = w["mean"].double()
+    P = w["P"][c].double()
+    mc = mean @ P[:, :3].T + P[:, 3]
+    x, y, z = (-mc / mc.norm(dim=1, keepdim=True)).unbind(1)
+    basis = torch.stack([torch.full_like(x, gft._SH_C0), gft._SH_C1 * y, gft._SH_C1 * z, gft._SH_C1 * x,
+                         gft._SH_C2[0] * x * y, gft._SH_C2[1] * y * z, gft._SH_C2[2] * (2 * z * z - x * x - y * y),
+                         gft._SH_C2[3] * x * z, gft._SH_C2[4] * (x * x - y * y)], 1)      # (N, 9)
+    return (basis.abs()[:, :, None] * w["color"].double().abs()).sum(1).numpy()        # (N, 3)
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_camera_inputs_match_reference_forward(name):
     """Arguments the reference's GS_model_with_param.forward hands to the Function (captured by
@@ -41,8 +54,12 @@ def test_camera_inputs_match_reference_forward(name):
             assert got.dtype == ref(theirs).dtype and np.array_equal(got, ref(theirs)), (c, mine)
         for mine, theirs in (("variance_inverse", "variance_inverse"), ("opacity", "opacity_sigmoid")):
             np.testing.assert_allclose(cam[mine].numpy(), ref(theirs), rtol=1e-6, atol=1e-7)
-        # l_d went through the build's own eval_sh on both sides (sh_utility.py is absent from the reference)
-        np.testing.assert_allclose(cam["l_d"].numpy(), ref("l_d_STAND_IN_SH"), rtol=1e-6, atol=1e-7)
+        # l_d went through the build's own eval_sh on both sides (sh_utility.py is absent from the reference).  It is a sum
+        # of SH terms that can cancel, and its fp32 inputs (camera-space means through a CPU matmul) differ in the last bits
+        # with the host's vector kernels: 1e-6 of the sum's condition scale, the rule tests/util.py states for sums.
+        scale = _sh_condition_scale(w, c)[cam["index"].numpy()]
+        err = np.abs(cam["l_d"].numpy().astype(np.float64) - ref("l_d_STAND_IN_SH"))
+        assert (err <= 1e-6 * scale + 1e-7).all(), (c, float(err.max()), float((err / scale).max()))
         assert int(ref("batch")[-1]) == cam["boxsize"].numel()  # the reference's single memory chunk
 
 
@@ -168,13 +185,14 @@ def test_colmap_round_trip(tmp_path):
         colmap_io.read_cameras(tmp_path / "cameras.bin")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/colmap/sparse/0"), reason="reference checkout not present")
 def test_colmap_reads_the_reference_scene():
-    """The files the reference's checkout does hold: 100 OPENCV cameras 640x427, 10 409 points."""
-    cams = colmap_io.read_cameras("/root/reference/colmap/sparse/0/cameras.bin")
+    """The files the reference's checkout does hold, byte for byte in tests/golden/colmap_scene
+    (make_colmap_fixture.py): 100 OPENCV cameras 640x427, 10 409 points."""
+    sparse = os.path.join(os.path.dirname(__file__), "golden", "colmap_scene", "sparse", "0")
+    cams = colmap_io.read_cameras(os.path.join(sparse, "cameras.bin"))
     assert len(cams) == 100 and {c["model"] for c in cams.values()} == {"OPENCV"}
     assert {(c["width"], c["height"]) for c in cams.values()} == {(640, 427)}
-    pts = colmap_io.read_points3d("/root/reference/colmap/sparse/0/points3D.bin")
+    pts = colmap_io.read_points3d(os.path.join(sparse, "points3D.bin"))
     assert pts["xyz"].shape == (10409, 3) and np.isfinite(pts["xyz"]).all() and len(np.unique(pts["id"])) == 10409
 
 

@@ -80,21 +80,32 @@ def test_oracle_bit_exact_vs_reference_golden(name):
 
 
 def test_oracle_vs_live_reference_host_build():
-    """Where oracle/_ref/ exists (built from /root/reference by oracle/Makefile) run the reference's
-    own forward kernels live against the C oracle on fresh inputs."""
+    """The reference's own forward kernels (host build) against the C oracle on fresh inputs, bit for bit: their outputs
+    as stored in golden/ref_host_golden.npz (make_ref_host_golden.py), and, where oracle/_ref/ was built by
+    oracle/Makefile, the live build as well."""
+    import hashlib
+
+    z = np.load(os.path.join(GOLD, "ref_host_golden.npz"))
+    ref = None
     ref_dir = os.path.join(os.path.dirname(os.path.dirname(__file__)), "oracle", "_ref")
-    if not os.path.exists(os.path.join(ref_dir, "grouped_cumprod_ref_host.so")):
-        pytest.skip("oracle/_ref/grouped_cumprod_ref_host.so not built")
-    sys.path.insert(0, ref_dir)
-    import grouped_cumprod_ref_host as ref
+    if os.path.exists(os.path.join(ref_dir, "grouped_cumprod_ref_host.so")):
+        sys.path.insert(0, ref_dir)
+        import grouped_cumprod_ref_host as ref
 
     for n, dist in [(1, "all1"), (777, "poisson8"), (50000, "geo80"), (50000, "mixed"), (9000, "one_run")]:
         key, x = make_keys(n, dist, n), make_values(n, n)
-        y = torch.zeros_like(x)
-        ref.grouped_cumprod_forward(x, key, y)
-        assert torch.equal(y, co.cumprod_forward(x, key))
-        ref.grouped_cumsum_forward(x, key, y)
-        assert torch.equal(y, co.cumsum_forward(x, key))
+        name = f"{n}_{dist}"
+        assert hashlib.sha256(key.numpy().tobytes() + x.numpy().tobytes()).hexdigest() == str(z[name + "/inputs_sha256"]), \
+            f"{name}: inputs differ from those the stored outputs were made from"
+        cp, cs = co.cumprod_forward(x, key), co.cumsum_forward(x, key)
+        assert np.array_equal(cp.numpy(), z[name + "/cumprod"]), name
+        assert np.array_equal(cs.numpy(), z[name + "/cumsum"]), name
+        if ref is not None:
+            y = torch.zeros_like(x)
+            ref.grouped_cumprod_forward(x, key, y)
+            assert torch.equal(y, cp)
+            ref.grouped_cumsum_forward(x, key, y)
+            assert torch.equal(y, cs)
 
 
 @pytest.mark.parametrize("dist", ["all1", "poisson8", "geo80", "mixed"])

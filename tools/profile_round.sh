@@ -9,12 +9,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 rm -rf $OUT && mkdir -p $OUT/stats $OUT/pmc_fetch $OUT/pmc_write $OUT/long_fetch $OUT/long_write $OUT/fn_pmc $OUT/fn_stats
 cd /tmp && export TMPDIR=/tmp
-echo "== plain bench"; python3 $ROOT/bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+echo "== plain bench"; python3 $ROOT/bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 echo "== kernel trace + stats of bench.py"
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o st --output-format csv -- python3 $ROOT/bench.py --cpu-sample 0 > $OUT/bench_stats.json 2> $OUT/bench_stats.err
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o st --output-format csv -- python3 $ROOT/bench.py --full --cpu-sample 0 > $OUT/bench_stats.json 2> $OUT/bench_stats.err
 export GCP_BENCH_NO_SHARDED=1
-echo "== pmc FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o p --output-format csv -- python3 $ROOT/bench.py --cpu-sample 0 --steps 20 > $OUT/pmc_fetch.json 2> $OUT/pmc_fetch.err
-echo "== pmc WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o p --output-format csv -- python3 $ROOT/bench.py --cpu-sample 0 --steps 20 > $OUT/pmc_write.json 2> $OUT/pmc_write.err
+echo "== pmc FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o p --output-format csv -- python3 $ROOT/bench.py --full --cpu-sample 0 --steps 20 > $OUT/pmc_fetch.json 2> $OUT/pmc_fetch.err
+echo "== pmc WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o p --output-format csv -- python3 $ROOT/bench.py --full --cpu-sample 0 --steps 20 > $OUT/pmc_write.json 2> $OUT/pmc_write.err
 echo "== long groups: timing, then traffic"
 python3 $ROOT/tools/pathological_bench.py > $OUT/long_groups.txt 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/long_fetch -o p --output-format csv -- python3 $ROOT/tools/pathological_bench.py "whole array" "5000" > /dev/null 2>&1
