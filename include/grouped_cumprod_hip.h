@@ -110,10 +110,17 @@ int gcp_cumsum_forward(const float* x, const int32_t* key, float* y, int64_t n,
  *              cuda_kernel/grouped_cumprod_backward.cu:9-41 (kernel), :43-65.
  * `inv` is the dense group id 0..G-1 of every element (non-decreasing runs),
  * `inv_len[g]` the exclusive end offset of group g (cuda_test.py:27).  The two
- * must describe the same partition (what gs_model.py / cuda_test.py pass); the
- * group ends are taken from the runs of `inv`, `inv_len` is only validated by
- * gcp_check_groups().  The reference's O(sum L^2) per-element loop is replaced
- * by one O(n) reverse segmented scan.  Traffic: 20 B / element.
+ * must describe the same partition (what gs_model.py / cuda_test.py pass;
+ * gcp_check_groups() verifies it).  The group ends are taken from `inv_len`:
+ * for every 1024-element range the kernel reads `inv` at the two ends only and
+ * the entries of `inv_len` between them.  A range where those do not describe
+ * the range exactly (ids outside [0, n_groups), ends out of order or not
+ * bracketing the range, more than 255 groups) takes its ends from the runs of
+ * `inv` instead; `inv_len` is never read outside [0, n_groups).  So a call with
+ * `inv` = any key with the right runs and a one-entry dummy `inv_len` is still
+ * served, at the old cost.  The reference's O(sum L^2) per-element loop is
+ * replaced by one O(n) reverse segmented scan.  Traffic: 16 B / element plus
+ * ~4 B per group (20 B / element on ranges that fall back to `inv`).
  */
 int gcp_cumprod_backward(const float* param, const float* param_cumprod,
                          const float* grad_out, const int32_t* inv, float* grad_in,

@@ -40,9 +40,11 @@
 //     workspace must be zeroed once (gcp_workspace_init).
 //   * The backward (a3) is the same machinery run in reverse index order on
 //     w[i] = grad_out[i] * cumprod[i] with the division by p'_j fused into the
-//     store: one O(n) pass, 20 B / element.
+//     store: one O(n) pass.  Its head flags come from the group ends `inv_len`
+//     (a few entries per wave) instead of per-element `inv`: 16 B / element
+//     (param, cumprod, grad_out, grad_in), 20 B where a wave falls back to `inv`.
 //
-// HBM-bound by construction (12 B or 20 B per element, ~10 VALU per element):
+// HBM-bound by construction (12 B or 16 B per element, ~10 VALU per element):
 // no MFMA.  All index arithmetic on the array is 64-bit.
 
 #include <hip/hip_runtime.h>
@@ -136,6 +138,8 @@ struct ScanArgs {
   const float* in1;  // param_cumprod (a3 only)
   const float* in2;  // grad_out (a3 only)
   const int* key;    // pixel key (a1/a2) or dense group id `inv` (a3)
+  const int* ends;   // a3: exclusive end offset of every group (`inv_len`), the source of the head flags
+  i64 n_groups;      // a3: entries of `ends`
   const float* carry;  // optional per-group prefix (indexed by `key`, which must then be the dense group id)
   const int* index;    // INDEXED scans: element i of the scan is in0[index[i]] and its result goes to out[index[i]]
   float* out;
@@ -294,11 +298,65 @@ __device__ __forceinline__ unsigned long long pack_desc(float agg, unsigned flag
 // ----------------------------------------------------------------------------
 // Main kernel: one tile per block.
 // ----------------------------------------------------------------------------
+// Backward head flags from the group ends.  Wave w of a tile owns the memory range [wlo, whi] (whi clipped to the
+// array); the ends falling inside it are read from `ends` (inv_len) — the groups ga = inv[wlo] .. gb = inv[whi], at most
+// 64 * kEndIters of them — and set as bits of a per-wave 1024-bit map in LDS.  Per wave, not per tile: no block
+// barrier in front of the local scans, and waves never wait for each other's lookups.  The map is taken only when
+// the operands describe the range exactly (the checks in group_ends); otherwise the wave compares neighbouring `inv`
+// as before.  Both give the same flags for a consistent (inv, inv_len) pair; the choice depends on the data only.
+constexpr int kEndIters = 4;
+constexpr int kBitWords = 256 * kRows / 32;  // words of one wave's map
+
+__device__ __forceinline__ void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Fills `bits` (bit i: element wlo + i is the last of its group) and returns true when the ends describe the wave's
+// range: 0 <= ga <= gb < n_groups, start(ga) <= wlo < end(ga), start(gb) <= whi < end(gb), the ends of ga-1 .. gb
+// strictly increasing.  `gend` = end(gb), the exclusive end of the group the wave's first element (scan order) is in.
+// Every `ends` index read lies in [ga - 1, gb] and so in [0, n_groups), whatever `inv` holds.
+__device__ __forceinline__ bool group_ends(const ScanArgs& a, unsigned* bits, i64 wlo, i64 whi, int ga, int gb, int lane,
+                                          i64& gend) {
+  if (lane < kBitWords) bits[lane] = 0u;
+  wave_sync_lds();
+  if (!(wlo <= whi && ga >= 0 && ga <= gb && (i64)gb < a.n_groups && (i64)gb - ga + 2 <= 64 * kEndIters)) return false;
+  const int last = gb - ga + 1;  // entry j is the end of group ga - 1 + j, j in [0, last]
+  int e[kEndIters];
+#pragma unroll
+  for (int it = 0; it < kEndIters; ++it) {  // all loads first: one round trip whatever the count
+    const int j = it * 64 + lane;
+    e[it] = 0;  // (j == 0 and ga == 0: the start of the array)
+    if (j <= last && ga - 1 + j >= 0) e[it] = a.ends[ga - 1 + j];
+  }
+  bool bad = false;
+  gend = 0;
+#pragma unroll
+  for (int it = 0; it < kEndIters; ++it) {
+    const int j = it * 64 + lane;
+    const int prev = dpp_i<0x138, 0xf>(it ? __builtin_amdgcn_readlane(e[it > 0 ? it - 1 : 0], 63) : 0, e[it]);  // entry j - 1
+    const i64 ej = e[it];
+    if (j >= 1 && j <= last) {
+      bad = bad || e[it] <= prev;
+      const i64 p = ej - 1;
+      if (p >= wlo && p <= whi) atomicOr(bits + ((p - wlo) >> 5), 1u << ((p - wlo) & 31));
+    }
+    if (j == 0) bad = bad || ej > wlo;
+    if (j == 1) bad = bad || ej <= wlo;
+    if (j == last - 1) bad = bad || ej > whi;
+    if (j == last) bad = bad || ej <= whi;
+    if ((last >> 6) == it) gend = (i64)__builtin_amdgcn_readlane(e[it], last & 63);
+  }
+  wave_sync_lds();
+  return __ballot(bad) == 0ull;
+}
+
 // FIXUP: the follow-up kernel re-runs a tile whose wait for the descriptor tree ran out, with the carry `fix_carry` it
 // took from the (completed) tree: same code, same association, so the tile gets the bits it would have got in time.
 template <int MODE, bool ALIGNED, bool FULL, bool CARRY, bool FIXUP = false, bool INDEXED = false, bool INPLACE = false>
 __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float* s_wv, int* s_wf,
-                                          float* s_tc, int* s_fh, const float fix_carry = 0.0f) {
+                                          float* s_tc, int* s_fh, unsigned* s_bits, const float fix_carry = 0.0f) {
   typedef Mode<MODE> MD;
   constexpr bool REV = MD::kRev;
   constexpr bool BWD = MD::kBwd;
@@ -314,6 +372,17 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   // descriptor set of this launch (parity of the workspace's launch counter); a scalar load issued first
   unsigned long long* const desc = a.desc_sets + (a.hdr[kHdrEpoch] & 1u);  // tile t at desc[2 t]
 
+  // backward: this wave's memory range and the groups at its two ends (wave-uniform loads, issued before the tile's data)
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  i64 wlo = 0, whi = -1;
+  int ga = 0, gb = -1;
+  if constexpr (BWD) {
+    wlo = base + kTile - (i64)(wu + 1) * WT;
+    whi = base + kTile - 1 - (i64)wu * WT;
+    if (whi > n - 1) whi = n - 1;
+    if (wlo <= whi) { ga = a.key[wlo]; gb = a.key[whi]; }
+  }
+
   // ---- issue all loads of this lane ------------------------------------
   // Streaming (non-temporal) loads are faster for bytes nobody reads again, but the END of a tile (scan
   // order) is what the next tile's look-back re-reads and must stay cached: GCP_NT_LOAD 0 = never,
@@ -326,13 +395,23 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   static_assert(!(INDEXED && BWD), "the backward has no indexed form");
   int4_t lb_ix;                    // (look-back gathers: only the values are used)
   i64 p0[kRows];
+  // the keys of this lane's elements (scan order); the backward loads them only where the group ends cannot be used
+  auto load_keys = [&](int r) {
+    if (FULL) {
+      if (nt_main) kk[r] = ld4<ALIGNED, true>(a.key + p0[r]);
+      else kk[r] = ld4<ALIGNED>(a.key + p0[r]);
+    } else {
+      kk[r] = ld4_guard(a.key, p0[r], n, 0);
+    }
+    kk[r] = to_scan_order<REV>(kk[r]);
+  };
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     const int q = w * WT + r * 256 + lane * 4;
     p0[r] = REV ? (base + kTile - 4 - q) : (base + q);
+    if constexpr (!BWD) load_keys(r);
     if (FULL) {
       if (nt_main) {  // wave-uniform
-        kk[r] = ld4<ALIGNED, true>(a.key + p0[r]);
         if constexpr (BWD) {
           v[r] = ld4<ALIGNED, true>(a.in2 + p0[r]) * ld4<ALIGNED, true>(a.in1 + p0[r]);
         } else if constexpr (INDEXED) {
@@ -341,7 +420,6 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
           v[r] = ld4<ALIGNED, true>(a.in0 + p0[r]);
         }
       } else {
-        kk[r] = ld4<ALIGNED>(a.key + p0[r]);
         if constexpr (BWD) {
           v[r] = ld4<ALIGNED>(a.in2 + p0[r]) * ld4<ALIGNED>(a.in1 + p0[r]);
         } else if constexpr (INDEXED) {
@@ -352,7 +430,6 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       }
       if constexpr (BWD) xp[r] = ld4<ALIGNED, (GCP_NT_LOAD != 0)>(a.in0 + p0[r]);  // param is never re-read by a look-back
     } else {
-      kk[r] = ld4_guard(a.key, p0[r], n, 0);
       if constexpr (BWD) {
         const float4_t g = ld4_guard(a.in2, p0[r], n, 0.0f);
         const float4_t c = ld4_guard(a.in1, p0[r], n, 0.0f);
@@ -365,7 +442,6 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       }
     }
     v[r] = to_scan_order<REV>(v[r]);
-    kk[r] = to_scan_order<REV>(kk[r]);
     if constexpr (BWD) xp[r] = to_scan_order<REV>(xp[r]);
   }
 
@@ -376,7 +452,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   // more memory behind the keys, and with a memory fault where it had not: found with rocgdb in round 3)
   const bool nb_exists = (pn >= 0) && (pn < n);
   int nbk = 0;
-  if (nb_exists) nbk = a.key[pn];
+  if (!BWD && nb_exists) nbk = a.key[pn];
 
   // look-back chunk 0 (wave 0 only): issued now so its latency overlaps
   const bool do_lb = !FIXUP && !INPLACE && (w == 0) && (lt > 0);  // (in place: see below)
@@ -391,10 +467,24 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       else if constexpr (INDEXED) lbv = ld4_indexed<ALIGNED, false>(a.in0, a.index, lbp, lb_ix);
       else lbv = ld4<ALIGNED>(a.in0 + lbp);
     } else {
-      lbk = ld4_guard(a.key, lbp, n, 0);
+      if constexpr (!BWD) lbk = ld4_guard(a.key, lbp, n, 0);
       if constexpr (BWD) lbv = ld4_guard(a.in2, lbp, n, 0.0f) * ld4_guard(a.in1, lbp, n, 0.0f);
       else if constexpr (INDEXED) lbv = ld4_indexed_guard(a.in0, a.index, lbp, n, id, lb_ix);
       else lbv = ld4_guard(a.in0, lbp, n, id);
+    }
+  }
+
+  // ---- backward: head flags from the group ends, else from the keys (wave-uniform choice) ----
+  bool from_ends = false;
+  i64 gend = 0;  // end of the group of the wave's first element (scan order): the look-back's membership bound
+  unsigned* const wbits = s_bits + kBitWords * wu;
+  if constexpr (BWD) {
+    from_ends = group_ends(a, wbits, wlo, whi, ga, gb, lane, gend);
+    if (!from_ends) {
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) load_keys(r);
+      if (nb_exists) nbk = a.key[pn];
+      if (do_lb) lbk = ld4_guard(a.key, lbp, n, 0);
     }
   }
 
@@ -415,7 +505,21 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     const int pk = dpp_i<0x138, 0xf>(lane0_prev, kk[r].w);  // wave_shr:1, lane 0 keeps old
 
     bool f0, f1, f2, f3;
-    if (FULL) {
+    if (BWD && from_ends) {
+      // bit i of the nibble: memory element p0[r] + i ends its group; scan item k is memory element p0[r] + 3 - k
+      const int off = WT - 4 - r * 256 - lane * 4;  // p0[r] - wlo
+      const unsigned nib = (wbits[off >> 5] >> (off & 31)) & 0xfu;
+      f0 = (nib >> 3) & 1u; f1 = (nib >> 2) & 1u; f2 = (nib >> 1) & 1u; f3 = nib & 1u;
+      if (FULL) {
+        f0 = f0 || ((lt == 0) && (w == 0) && (r == 0) && (lane == 0));
+      } else {
+        const i64 p = p0[r];  // items 3..0 are p .. p + 3; the last element of the array is a head
+        f0 = (p + 3 < n) && (f0 || p + 3 == n - 1);
+        f1 = (p + 2 < n) && (f1 || p + 2 == n - 1);
+        f2 = (p + 1 < n) && (f2 || p + 1 == n - 1);
+        f3 = (p + 0 < n) && (f3 || p + 0 == n - 1);
+      }
+    } else if (FULL) {
       const bool first_of_array = (lt == 0) && (w == 0) && (r == 0) && (lane == 0);
       f0 = first_of_array || (kk[r].x != pk);
       f1 = kk[r].y != kk[r].x;
@@ -489,7 +593,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     float tc = FIXUP ? fix_carry : id;
     int unresolved = 0;
     if (do_lb) {
-      const int k0 = __builtin_amdgcn_readfirstlane(kk[0].x);
+      const int k0 = from_ends ? 0 : __builtin_amdgcn_readfirstlane(kk[0].x);
+      // (backward on the group ends: element p continues the tile's first group iff p < gend; do_lb: a full tile)
       // returns true when the look-back is finished (group start found, or array end)
       auto process = [&](float4_t cv, int4_t ck, i64 cp, int j) -> bool {
         // scan-order distance of item k of this lane: j*256 + lane*4 + k + 1
@@ -498,6 +603,9 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
         bool c0, c1, c2, c3;
         if (!REV) {
           c0 = lk.x == k0; c1 = lk.y == k0; c2 = lk.z == k0; c3 = lk.w == k0;
+        } else if (BWD && from_ends) {
+          const i64 m = (gend < n ? gend : n) - cp;  // items of this lane inside the group (and the array)
+          c0 = m > 0; c1 = m > 1; c2 = m > 2; c3 = m > 3;
         } else {
           c0 = (cp + 0 < n) && lk.x == k0; c1 = (cp + 1 < n) && lk.y == k0;
           c2 = (cp + 2 < n) && lk.z == k0; c3 = (cp + 3 < n) && lk.w == k0;
@@ -533,7 +641,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
             else if constexpr (INDEXED) cv[c] = ld4_indexed<ALIGNED, false>(a.in0, a.index, cp[c], lb_ix);
             else cv[c] = ld4<ALIGNED>(a.in0 + cp[c]);
           } else {
-            ck[c] = ld4_guard(a.key, cp[c], n, 0);
+            ck[c] = int4_t{0, 0, 0, 0};
+            if (!(BWD && from_ends)) ck[c] = ld4_guard(a.key, cp[c], n, 0);
             if constexpr (BWD) cv[c] = ld4_guard(a.in2, cp[c], n, 0.0f) * ld4_guard(a.in1, cp[c], n, 0.0f);
             else if constexpr (INDEXED) cv[c] = ld4_indexed_guard(a.in0, a.index, cp[c], n, id, lb_ix);
             else cv[c] = ld4_guard(a.in0, cp[c], n, id);
@@ -740,10 +849,11 @@ void gcp_scan_main(const ScanArgs a) {
   __shared__ int s_wf[kWaves + 2];
   __shared__ float s_tc[1];
   __shared__ int s_fh[kWaves];
+  __shared__ unsigned s_bits[Mode<MODE>::kBwd ? kWaves * kBitWords : 1];
   const i64 lt = logical_tile((i64)blockIdx.x, a.ntiles, a.xcd_remap);
   const i64 pt = Mode<MODE>::kRev ? (a.ntiles - 1 - lt) : lt;
-  if ((pt + 1) * (i64)kTile <= a.n) scan_tile<MODE, ALIGNED, true, CARRY, false, INDEXED, INPLACE>(a, lt, s_wv, s_wf, s_tc, s_fh);
-  else scan_tile<MODE, ALIGNED, false, CARRY, false, INDEXED, INPLACE>(a, lt, s_wv, s_wf, s_tc, s_fh);
+  if ((pt + 1) * (i64)kTile <= a.n) scan_tile<MODE, ALIGNED, true, CARRY, false, INDEXED, INPLACE>(a, lt, s_wv, s_wf, s_tc, s_fh, s_bits);
+  else scan_tile<MODE, ALIGNED, false, CARRY, false, INDEXED, INPLACE>(a, lt, s_wv, s_wf, s_tc, s_fh, s_bits);
 }
 
 // ----------------------------------------------------------------------------
@@ -832,6 +942,7 @@ __global__ __launch_bounds__(kThreads) void gcp_fallback(const ScanArgs a) {
   __shared__ int s_wf[kWaves + 2];
   __shared__ float s_tc[1];
   __shared__ int s_fh[kWaves];
+  __shared__ unsigned s_bits[MD::kBwd ? kWaves * kBitWords : 1];
   __shared__ int s_any, s_tree, s_cnt;
   __shared__ int s_tile[64];
   __shared__ float s_carry;
@@ -896,7 +1007,7 @@ __global__ __launch_bounds__(kThreads) void gcp_fallback(const ScanArgs a) {
           __syncthreads();
           const float c = s_carry;
           // guarded dword form of the tile routine: the same arithmetic as the vector form on any alignment and tile
-          scan_tile<MODE, false, false, CARRY, true, INDEXED>(a, lt, s_wv, s_wf, s_tc, s_fh, c);
+          scan_tile<MODE, false, false, CARRY, true, INDEXED>(a, lt, s_wv, s_wf, s_tc, s_fh, s_bits, c);
           __syncthreads();
         }
         __syncthreads();
@@ -1099,12 +1210,13 @@ int env_int(const char* name, int dflt) {
 
 template <int MODE>
 int launch_scan(const float* in0, const float* in1, const float* in2, const int* key, float* out,
-                i64 n, void* ws, size_t ws_bytes, void* stream_, const float* carry = nullptr, const int* index = nullptr) {
+                i64 n, void* ws, size_t ws_bytes, void* stream_, const float* carry = nullptr, const int* index = nullptr,
+                const int* ends = nullptr, i64 n_groups = 0) {
   hipStream_t stream = (hipStream_t)stream_;
   if (n < 0) return GCP_ERR_INVALID_ARGUMENT;
   if (n == 0) return GCP_OK;
   if (!in0 || !key || !out) return GCP_ERR_INVALID_ARGUMENT;
-  if (Mode<MODE>::kBwd && (!in1 || !in2)) return GCP_ERR_INVALID_ARGUMENT;
+  if (Mode<MODE>::kBwd && (!in1 || !in2 || !ends || n_groups <= 0)) return GCP_ERR_INVALID_ARGUMENT;
   // No aliasing: the look-back re-reads the neighbouring tile's RAW inputs while that tile's block may already be
   // storing its outputs, so an output range that shares bytes with an input range races between blocks.
   // Exactly in place (out == x) is served — the reference's thrust::inclusive_scan_by_key allows it
@@ -1117,6 +1229,8 @@ int launch_scan(const float* in0, const float* in1, const float* in2, const int*
       const uintptr_t q0 = (uintptr_t)q;
       if (q && o0 < q0 + (uintptr_t)n * 4u && q0 < o1) return GCP_ERR_INVALID_ARGUMENT;
     }
+    const uintptr_t e0 = (uintptr_t)ends;  // the group ends: n_groups entries
+    if (ends && o0 < e0 + (uintptr_t)n_groups * 4u && e0 < o1) return GCP_ERR_INVALID_ARGUMENT;
   }
   const i64 ntiles = (n + kTile - 1) / kTile;
   if (ntiles > 0x7fffffffLL) return GCP_ERR_INVALID_ARGUMENT;
@@ -1131,6 +1245,7 @@ int launch_scan(const float* in0, const float* in1, const float* in2, const int*
   char* p = (char*)ws;
   ScanArgs a;
   a.in0 = in0; a.in1 = in1; a.in2 = in2; a.key = key; a.out = out; a.carry = carry; a.index = index;
+  a.ends = ends; a.n_groups = n_groups;
   a.n = n; a.ntiles = ntiles;
   a.hdr = (unsigned*)p; p += kWsHeaderBytes;
   a.desc_sets = (unsigned long long*)p;
@@ -1301,7 +1416,7 @@ int gcp_cumprod_backward(const float* param, const float* param_cumprod, const f
                          int64_t n_groups, void* ws, size_t ws_bytes, void* stream) {
   if (n > 0 && (!inv_len || n_groups <= 0)) return GCP_ERR_INVALID_ARGUMENT;
   return launch_scan<M_CUMPROD_BWD>(param, param_cumprod, grad_out, inv, grad_in, n, ws, ws_bytes,
-                                    stream);
+                                    stream, nullptr, nullptr, inv_len, n_groups);
 }
 
 int gcp_check_groups(const int32_t* inv, const int32_t* inv_len, int64_t n, int64_t n_groups,

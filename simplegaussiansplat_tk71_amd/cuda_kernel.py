@@ -234,8 +234,9 @@ class GroupedCumprod(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, y, key = ctx.saved_tensors
         grad_x = torch.empty_like(x)
-        # The kernel reads group ends from the runs of `inv`; the key array itself has
-        # the same runs, and inv_len is only part of the reference signature.
+        # No group ends here: with a one-entry dummy inv_len every range of the kernel
+        # fails its check and takes the ends from the runs of `inv`, which the key
+        # array has too.
         inv_len = torch.zeros(1, dtype=torch.int32, device=x.device)
         _ext.grouped_cumprod_backward(x, y, grad_y.contiguous(), key, grad_x, inv_len)
         return grad_x, None

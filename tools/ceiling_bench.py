@@ -25,6 +25,7 @@ def main():
     lib = ctypes.CDLL(so)
     lib.ceiling12.argtypes = [V, V, V, ctypes.c_longlong, ctypes.c_int, V]
     lib.ceiling20.argtypes = [V, V, V, V, V, ctypes.c_longlong, ctypes.c_int, V]
+    lib.ceiling16.argtypes = [V, V, V, V, ctypes.c_longlong, ctypes.c_int, V]
     p = synthetic.make_config("cfg3", seed=0, device=dev)
     m = p.n_pairs
     y, g = torch.empty_like(p.x), torch.empty_like(p.x)
@@ -37,7 +38,10 @@ def main():
         "ideal 20B (4R+1W)": (lambda: lib.ceiling20(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), p.inv.data_ptr(), g.data_ptr(), m, 0, st), 20),
         "ideal 20B nt-store": (lambda: lib.ceiling20(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), p.inv.data_ptr(), g.data_ptr(), m, 1, st), 20),
         "ideal 20B nt-ld+st": (lambda: lib.ceiling20(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), p.inv.data_ptr(), g.data_ptr(), m, 2, st), 20),
-        "cumprod_bwd": (lambda: gc.grouped_cumprod_backward(p.x, y, p.grad_out, p.inv, g, p.inv_len), 20),
+        "ideal 16B (3R+1W)": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 0, st), 16),
+        "ideal 16B nt-store": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 1, st), 16),
+        "ideal 16B nt-ld+st": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 2, st), 16),
+        "cumprod_bwd": (lambda: gc.grouped_cumprod_backward(p.x, y, p.grad_out, p.inv, g, p.inv_len), 16),  # group ends from inv_len
     }
     res = {k: [] for k in ops}
     for _ in range(3):
