@@ -66,13 +66,12 @@ def is_stale():
     return built_hash() != source_hash()
 
 
-def build_hip_library(force=False, verbose=False, extra_flags=()):
+def build_hip_library(force=False, verbose=False):
     """Compile the HIP library in-tree; returns its path."""
     if not force and not is_stale():
         return LIB_PATH
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [find_hipcc(), *HIPCC_FLAGS, *extra_flags, f'-DGCP_SOURCE_HASH="{source_hash()}"', "-I", INCLUDE, "-o", LIB_PATH,
-           *SRCS]
+    cmd = [find_hipcc(), *HIPCC_FLAGS, f'-DGCP_SOURCE_HASH="{source_hash()}"', "-I", INCLUDE, "-o", LIB_PATH, *SRCS]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)

@@ -73,20 +73,12 @@ __global__ __launch_bounds__(256) void k_pixels_range(const void* __restrict__ r
 // _create_alpha_brend_min is called on, gs_model.py:609), so with values the blocks take the list back to front.  Any other
 // values: same result, more atomics.  All sixteen looks of a thread are issued before the first atomic (a look behind an
 // atomic waits for it: the compiler cannot move a load over an atomic that may hit the same address).
-#ifndef GCP_PIXELS_LOOK
-#define GCP_PIXELS_LOOK 1      // measurement switches (tools/build_variant.py): 0 = every pair issues its atomic
-#endif
-#ifndef GCP_PIXELS_FILTER_FROM
-#define GCP_PIXELS_FILTER_FROM (1 << 25)  // pairs from which the looks go to the 16-bit filter table (below: to the cells themselves)
-#endif
-#ifndef GCP_PIXELS_REVERSE
-#define GCP_PIXELS_REVERSE 1   // 0 = values front to back as well
-#endif
+constexpr int64_t kFilterFrom = 1 << 25;  // pairs from which the looks go to the 16-bit filter table (below: to the cells themselves)
 template <bool I64, bool INDEX, bool FILTER>
 __global__ __launch_bounds__(256) void k_pixels_min(const void* __restrict__ rects, const float* __restrict__ values, i64 n, int w1, int h1,
                                                     unsigned* __restrict__ cell, unsigned short* __restrict__ filter, int* __restrict__ info) {
   constexpr int kSteps = kPairTile / 256;  // 16
-  const i64 tile = (!INDEX && GCP_PIXELS_REVERSE) ? (i64)gridDim.x - 1 - blockIdx.x : (i64)blockIdx.x;
+  const i64 tile = !INDEX ? (i64)gridDim.x - 1 - blockIdx.x : (i64)blockIdx.x;
   // lane l of a wave takes pair (wave's 64 * step) + l: the 64 cells one instruction looks at are those of 64 CONSECUTIVE
   // pairs — five box rows of thirteen neighbouring cells, some seven cache lines (with four consecutive pairs per lane, the
   // shape of the wide loads, every instruction touched the rows of 256 pairs: 1.0 instead of 0.6 ms at 1.65e8 pairs)
@@ -139,13 +131,11 @@ __global__ __launch_bounds__(256) void k_pixels_min(const void* __restrict__ rec
       }
     }
   } else {
-    if (GCP_PIXELS_LOOK) {
 #pragma unroll
-      for (int s = 0; s < kSteps; ++s) seen[s] = __hip_atomic_load(cell + at[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    for (int s = 0; s < kSteps; ++s) seen[s] = __hip_atomic_load(cell + at[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) {
-      if (((live >> s) & 1u) && (!GCP_PIXELS_LOOK || seen[s] > u[s])) atomicMin(cell + at[s], u[s]);
+      if (((live >> s) & 1u) && seen[s] > u[s]) atomicMin(cell + at[s], u[s]);
     }
   }
   if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) {
@@ -278,7 +268,7 @@ int gcp_pixels_min(const void* rects_xy, int32_t rects_are_int64, const float* v
   GCP_HIP(hipMemsetD32Async((hipDeviceptr_t)cell, (int)kNoPair, (size_t)(w1 * h1), stream));
   unsigned short* const filter = (unsigned short*)(base + L.filter);
   const char* ff = getenv("GCP_PIXELS_FILTER_FROM");  // read per call: the tests switch it inside one process
-  const bool use_filter = n >= ((ff && *ff) ? (int64_t)atoll(ff) : (int64_t)GCP_PIXELS_FILTER_FROM);
+  const bool use_filter = n >= ((ff && *ff) ? (int64_t)atoll(ff) : kFilterFrom);
   if (use_filter) GCP_HIP(hipMemsetD16Async((hipDeviceptr_t)filter, (unsigned short)0xffff, (size_t)(w1 * h1), stream));
   const unsigned pair_blocks = (unsigned)((n + kPairTile - 1) / kPairTile);
   const bool wide = rects_are_int64 != 0, index = values == nullptr;

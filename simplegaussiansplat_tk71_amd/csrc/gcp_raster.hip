@@ -52,32 +52,11 @@
 namespace {
 using namespace gcp;
 
-#ifndef GCP_STAGE_BWD
-#define GCP_STAGE_BWD 32
-#endif
-constexpr int kTile = 16;           // tile edge in pixels; 256 pixels = one block, 4 rows per wave
-// Measurement builds only (tools/build_variant.py -DGCP_TILE_SX=5|6): tiles of 32 x 8 / 64 x 4 pixels for the binning and the
-// tile-list walk — the blend kernels are NOT valid in such a build.  DESIGN.md §3.4 "the walk's access shape".
-#ifndef GCP_TILE_SX
-#define GCP_TILE_SX 4
-#endif
-// -DGCP_TILE_SX=5 -DGCP_TILE_SY=4: "super-tiles" of 32 x 16 pixels walked by 512-thread blocks — eight waves of 4 rows x 16
-// columns each, two side by side — so that both pieces of a box row that crosses a 16-pixel column boundary are read and
-// written by one block in the same round.
-#ifndef GCP_TILE_SY
-#define GCP_TILE_SY (8 - GCP_TILE_SX)
-#endif
-constexpr int kTileSX = GCP_TILE_SX, kTileSY = GCP_TILE_SY;
-constexpr int kTileW = 1 << kTileSX, kTileH = 1 << kTileSY;
-constexpr int kWalkThreads = kTileW * kTileH;           // one lane per pixel of the walk's tile
-constexpr bool kWalkSuper = kWalkThreads == 512;
-#ifndef GCP_WALK_DENSE
-#define GCP_WALK_DENSE 0  // measurement builds: the dense walk below (one wave per tile of any shape up to 1024 pixels)
-#endif
-static_assert(GCP_WALK_DENSE || kWalkThreads == 256 || (kTileSX == 5 && kTileSY == 4), "walk tiles: 256 pixels, or 32 x 16 super-tiles");
+constexpr int kTileLog2 = 4;
+constexpr int kTile = 1 << kTileLog2;  // tile edge in pixels; 256 pixels = one block, 4 rows per wave
 constexpr int kStage = 256;         // list entries staged per LDS round (forward)
-constexpr int kStageBwd = GCP_STAGE_BWD;       // (backward; LDS also holds the per-pixel-row partial sums)
-constexpr int kCkpt = kStageBwd;               // the forward saves every pixel's transmittance every kCkpt list entries
+constexpr int kStageBwd = 32;       // (backward; LDS also holds the per-pixel-row partial sums)
+constexpr int kCkpt = kStageBwd;    // the forward saves every pixel's transmittance every kCkpt list entries
 static_assert(kStage % kCkpt == 0 && 64 % kCkpt == 0 && kCkpt <= 32, "checkpoints fall on hit-word boundaries");
 constexpr int kGradVals = 9;        // per (tile, Gaussian) slot: go, gl0..2, S(c dx), S(c dy), S(c dx dx), S(c dx dy), S(c dy dy)
 constexpr int kRowVals = 7;         // per pixel row in LDS: go, gl0..2, S(c), S(c dx), S(c dx dx)   (dy is constant along a row)
@@ -102,7 +81,7 @@ __device__ __forceinline__ float xchg_sum(bool second, float a, float b) {
 }
 
 struct TileGrid { int tx, ty; };
-inline TileGrid tile_grid(int W, int H) { return {(W + 1 + kTileW - 1) / kTileW, (H + 1 + kTileH - 1) / kTileH}; }
+inline TileGrid tile_grid(int W, int H) { return {(W + 1 + kTile - 1) / kTile, (H + 1 + kTile - 1) / kTile}; }
 
 // ------------------------------------------------------------------------------------------
 // Exclusive prefix sum of int32 (out has n+1 entries, out[n] = total).  Two small launches.
@@ -188,7 +167,7 @@ __global__ __launch_bounds__(256) void k_tile_count(const int* start, const int*
     Box b;
     int c = 0;
     if (load_box(start, end, g, W, H, b))
-      c = ((b.x1 >> kTileSX) - (b.x0 >> kTileSX) + 1) * ((b.y1 >> kTileSY) - (b.y0 >> kTileSY) + 1);
+      c = ((b.x1 >> kTileLog2) - (b.x0 >> kTileLog2) + 1) * ((b.y1 >> kTileLog2) - (b.y0 >> kTileLog2) + 1);
     cnt[g] = c;
     wide += (unsigned long long)c;
   }
@@ -222,8 +201,8 @@ __global__ __launch_bounds__(256) void k_tile_emit(const int* start, const int* 
   }
   Box b = {0, 0, -1, -1};
   if (live) live = load_box(start, end, g, W, H, b);
-  const int tx0 = b.x0 >> kTileSX, ty0 = b.y0 >> kTileSY;
-  const int ntx = live ? (b.x1 >> kTileSX) - tx0 + 1 : 0, nty = live ? (b.y1 >> kTileSY) - ty0 + 1 : 0;
+  const int tx0 = b.x0 >> kTileLog2, ty0 = b.y0 >> kTileLog2;
+  const int ntx = live ? (b.x1 >> kTileLog2) - tx0 + 1 : 0, nty = live ? (b.y1 >> kTileLog2) - ty0 + 1 : 0;
   const int e0 = live ? off[g] : 0;
   const bool wide = ntx * nty >= kEmitWide;
   if (live && !wide) {
@@ -387,10 +366,8 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const unsigned* key, const
 // Same result as the chunk-at-a-time kernels bit for bit: integer arithmetic only, and the one fetch-add whose RETURN value
 // is used (a digit's running count inside a wave) has a single lane per address and instruction, in program order.
 // ------------------------------------------------------------------------------------------
-#ifndef GCP_SORT_BIG
-#define GCP_SORT_BIG 4096  // (8192 with 16 waves and one block per CU: passes 0 / 1 no faster, measured)
-#endif
-constexpr int kBigChunk = GCP_SORT_BIG;  // keys staged through LDS at a time by the M-sized sort
+constexpr int kBigChunk = 4096;  // keys staged through LDS at a time by the M-sized sort (8192 with 16 waves and one block
+                                 // per CU: passes 0 / 1 no faster, measured)
 constexpr int kSortSub = 8;  // chunks per super-chunk at most
 
 // digit counts of one wave's 64 keys into `h`: lanes with the same digit as their left neighbour are counted by the
@@ -660,20 +637,6 @@ __device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
          (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-#ifndef GCP_DPP_ASM
-#define GCP_DPP_ASM 1
-#endif
-#ifndef GCP_BLEND_FMA
-#define GCP_BLEND_FMA 1
-#endif
-#if GCP_BLEND_FMA
-// The blend kernels are VALU-issue bound: let a*b+c contract into v_fma_f32 here (the library is otherwise built
-// with -ffp-contract=off).  One rounding instead of two per contraction; results stay within the 1e-5 bar.
-#define GCP_FP_CONTRACT _Pragma("clang fp contract(fast)")
-#else
-#define GCP_FP_CONTRACT
-#endif
-
 // Transmittance checkpoints: slot q of tile t holds every pixel's transmittance in front of list entry first + q kCkpt,
 // for q = 0 .. ceil(n / kCkpt) — the last one is the transmittance behind the whole list — 256 floats each (one per
 // pixel of the tile, thread order).  Tile t's slots start at first / kCkpt + 2 t: consecutive tiles never overlap
@@ -686,7 +649,9 @@ inline size_t ckpt_floats(i64 n_tile_pairs, int n_tiles) {
 
 template <bool CKPT>
 __global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __restrict__ image, float* __restrict__ t_ckpt) {
-  GCP_FP_CONTRACT
+  // The blend kernels are VALU-issue bound: let a*b+c contract into v_fma_f32 here (the library is otherwise built
+  // with -ffp-contract=off).  One rounding instead of two per contraction; results stay within the 1e-5 bar.
+#pragma clang fp contract(fast)
   __shared__ Staged<kStage> s;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave id in an SGPR: the row test below is scalar
@@ -788,14 +753,11 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
                                                    const float* __restrict__ t_ckpt,
                                                    const float* __restrict__ grad_image,
                                                    float* __restrict__ partial /*[K][kGradVals]*/) {
-  GCP_FP_CONTRACT
+#pragma clang fp contract(fast)  // as in k_blend_fwd
   __shared__ Staged<kStageBwd> s;
   // [entry][pixel row of the tile * kRowSlots + value]; one word of padding per entry: the fold below reads with one
   // thread per entry, and a stride of 128 words would put all of them on one LDS bank
-#ifndef GCP_PART_PAD
-#define GCP_PART_PAD 1
-#endif
-  constexpr int kPartStride = 16 * kRowSlots + GCP_PART_PAD;
+  constexpr int kPartStride = 16 * kRowSlots + 1;
   __shared__ float s_part[kStageBwd][kPartStride];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave id in an SGPR: the row test below is scalar
@@ -812,9 +774,6 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
   }
   const unsigned lane_bits = (1u << (lane & 15)) | (1u << (16 + w * 4 + (lane >> 4)));
   const bool b1 = lane & 2;
-#if !GCP_DPP_ASM
-  const bool b3 = lane & 8, b2 = lane & 4;
-#endif
   float* const row_slot = &s_part[0][(w * 4 + (lane >> 4)) * kRowSlots + ((lane & 2) ? 4 : 0) + ((lane & 4) ? 2 : 0) + ((lane & 8) ? 1 : 0)];
   const float* const ck = t_ckpt + ckpt_slot0(first, tile) * 256 + threadIdx.x;
   static_assert(kStageBwd <= 32, "one 32-bit word of hits per wave");
@@ -896,7 +855,6 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
         // writing one destination do "keep + partner's copy" for both classes without a select (7 + 4 VALU); the last
         // two need selects (3 + 1).  15 VALU instead of 7 x 4 = 28.
         float q0, q1, q2, q3, p0, p1;
-#if GCP_DPP_ASM
         // s_nop 1: a DPP source written by the preceding VALU instruction needs two wait states
         asm volatile(
             "s_nop 1\n\t"
@@ -917,14 +875,6 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
             "v_add_f32_dpp %1, %5, %5 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
             : "=&v"(p0), "=&v"(p1)
             : "v"(q0), "v"(q1), "v"(q2), "v"(q3));
-#else
-        q0 = xchg_sum<0x140>(b3, r_o, r_l0);     // b3 = 0 lanes: go     | b3 = 1: gl0
-        q1 = xchg_sum<0x140>(b3, r_l1, r_l2);    //               gl1    |         gl2
-        q2 = xchg_sum<0x140>(b3, r_c, r_cx);     //               S(c)   |         S(c dx)
-        q3 = r_xx + dpp_f<0x140, 0xf>(0.0f, r_xx);  // S(c dx dx) in both classes; the b3 = 1 copy lands in slot 7
-        p0 = xchg_sum<0x141>(b2, q0, q1);
-        p1 = xchg_sum<0x141>(b2, q2, q3);
-#endif
         const float o0 = xchg_sum<0x4e>(b1, p0, p1);
         const float tot = o0 + dpp_f<0xb1, 0xf>(0.0f, o0);
         row_slot[kc * kPartStride] = tot;  // lanes i and i^1 store the same word
@@ -1092,13 +1042,7 @@ __global__ __launch_bounds__(256) void k_pixel_lists(const BlendArgs a, int* __r
 // index array: 8 B per pair.  Lanes of one pixel row read and write consecutive addresses (64 B per box row and tile).
 // ------------------------------------------------------------------------------------------
 constexpr int kWalkStage = 64;  // list entries staged per round: one hit word per wave
-#ifndef GCP_WALK_BATCH
-#define GCP_WALK_BATCH 8
-#endif
-#ifndef GCP_WALK_DBG
-#define GCP_WALK_DBG 0  // measurement builds only (tools/build_variant.py): 1 = no loads, 2 = no stores — DESIGN.md §3.4's split
-#endif
-constexpr int kWalkBatch = GCP_WALK_BATCH;  // listed entries whose loads are in flight together
+constexpr int kWalkBatch = 8;   // listed entries whose loads are in flight together
 
 // A batch: kWalkBatch listed entries of one wave's hit word.  The staged records are read together and the values
 // loaded together (walk_load); walk_fold then multiplies / adds them in list order and stores the running values.
@@ -1132,22 +1076,10 @@ __device__ __forceinline__ void walk_load(WalkBatch& b, unsigned long long& hits
 #pragma unroll
   for (int u = 0; u < kWalkBatch; ++u) {
     asm volatile("" :: "v"(e[u].x), "v"(e[u].y));  // the whole record is read ahead of the membership test
-#if GCP_TILE_SX == 4
     b.in[u] = ((unsigned)e[u].z & lane_bits) == lane_bits;
-#elif GCP_TILE_SX == 5
-    // 32 x 8 tiles, two pixel rows per wave: z = the box over the tile's 32 columns, w = over its 8 rows
-    b.in[u] = (((unsigned)e[u].z & lane_bits) != 0u) & (((unsigned)e[u].w & (1u << ly)) != 0u);
-#else
-    // 64 x 4 tiles, one pixel row per wave (the hit word has decided the row): (z, w) = the box over the tile's 64 columns
-    b.in[u] = ((((int)(threadIdx.x & 32) ? (unsigned)e[u].w : (unsigned)e[u].z) & lane_bits) != 0u);
-#endif
     const unsigned o = (unsigned)e[u].x + (unsigned)lxo + __umul24((unsigned)ly, (unsigned)e[u].y);
     b.off[u] = b.in[u] ? o : 0u;
-#if (GCP_WALK_DBG & 1)
-    b.v[u] = __int_as_float(0x3f7fff00 + b.off[u] % 7);
-#else
     b.v[u] = WIDE ? x[b.off[u]] : *(const float*)((const char*)x + b.off[u]);
-#endif
   }
 }
 // COUNT: how many of the values just written are exactly 0 — what the `!= 0` compaction that follows drops
@@ -1185,13 +1117,8 @@ __device__ __forceinline__ void walk_fold(const WalkBatch& b, float* __restrict_
       acc = (MODE == 0) ? acc * b.v[u] : acc + b.v[u];
       drop = acc == 0.0f;  // NaN is kept, as `!= 0` keeps it
       const float res = (OUT != kWalkFinal) ? acc : (MODE == 0 ? acc / b.v[u] : acc - b.v[u]);
-#if (GCP_WALK_DBG & 2)
-      if (acc == 12345.678f)
-#endif
-      {
-        if (WIDE) out[b.off[u]] = res;
-        else *(float*)((char*)out + b.off[u]) = res;
-      }
+      if (WIDE) out[b.off[u]] = res;
+      else *(float*)((char*)out + b.off[u]) = res;
     }
     if (OUT != kWalkInclusive) {
       if (OUT == kWalkFinal && __ballot(drop) != 0ull) {  // wave-uniform: no store instruction at all where nothing drops
@@ -1236,13 +1163,7 @@ __device__ __forceinline__ void walk_dead(unsigned long long hits, const int4* _
     const int k = __builtin_ctzll(hits);
     hits &= hits - 1ull;
     const int4 e = ent[k];
-#if GCP_TILE_SX == 4
     const bool in = ((unsigned)e.z & lane_bits) == lane_bits;
-#elif GCP_TILE_SX == 5
-    const bool in = (((unsigned)e.z & lane_bits) != 0u) & (((unsigned)e.w & (1u << ly)) != 0u);
-#else
-    const bool in = ((((int)(threadIdx.x & 32) ? (unsigned)e.w : (unsigned)e.z) & lane_bits) != 0u);
-#endif
     const unsigned o = (unsigned)e.x + (unsigned)lxo + __umul24((unsigned)ly, (unsigned)e.y);
     if (in) keep[WIDE ? o : (o >> 2)] = 0;
     walk_count_dropped<WIDE>(in, in ? o : 0u, dropped);
@@ -1251,16 +1172,16 @@ __device__ __forceinline__ void walk_dead(unsigned long long hits, const int4* _
 
 template <int MODE, bool WIDE, int OUT>  // MODE 0 cumprod, 1 cumsum, 2 reverse cumsum; WIDE: more than 2^30 pairs
 // (pinned to eight waves per SIMD the byte-offset form fits 63 VGPRs without a spill — and runs no faster: 0.62 ms either way)
-__global__ __launch_bounds__(kWalkThreads) void k_pairs_scan_boxes(const BlendArgs a, const int* __restrict__ box_off,
-                                                                   const float* __restrict__ x, float* __restrict__ out,
-                                                                   int* __restrict__ dropped, unsigned char* __restrict__ keep,
-                                                                   int n_tiles, int xcd_remap) {
+__global__ __launch_bounds__(256) void k_pairs_scan_boxes(const BlendArgs a, const int* __restrict__ box_off,
+                                                          const float* __restrict__ x, float* __restrict__ out,
+                                                          int* __restrict__ dropped, unsigned char* __restrict__ keep,
+                                                          int n_tiles, int xcd_remap) {
   // a staged entry: x = position of the tile's first pixel in the entry's box run (box_off + (tile_y0 - y0) * width +
   // (tile_x0 - x0), may lie before the run), y = box width — both in bytes unless WIDE —, z = the box as bits over the
   // tile's columns (0-15) and rows (16-31).  A lane's pair is x + row * y + column, and it is in the box when both of
   // its bits are set: membership is one AND and one compare.
   __shared__ int4 s_ent_[kWalkStage + 1];
-  __shared__ unsigned long long s_hits[kWalkThreads / 64];
+  __shared__ unsigned long long s_hits[4];
   int4* const s_ent = s_ent_ + 1;  // record -1: no bits set, what a batch reads for the slots past its last hit
   if (threadIdx.x == 0) s_ent[-1] = make_int4(0, 0, 0, 0);
   const int lane = threadIdx.x & 63;
@@ -1272,17 +1193,11 @@ __global__ __launch_bounds__(kWalkThreads) void k_pairs_scan_boxes(const BlendAr
   // is written from two.
   const int tile = walk_tile(blockIdx.x, n_tiles, a.tiles_x, xcd_remap);
   if (tile < 0) return;
-  const int tile_x0 = (tile % a.tiles_x) * kTileW, tile_y0 = (tile / a.tiles_x) * kTileH;
+  const int tile_x0 = (tile % a.tiles_x) * kTile, tile_y0 = (tile / a.tiles_x) * kTile;
   constexpr int kUnit = WIDE ? 1 : 4;
-  // pixel rows per wave: 4 (16 x 16 tiles, and super-tiles: two waves side by side), 2 (32 x 8), 1 (64 x 4)
-  constexpr int kWaveCols = kWalkSuper ? 16 : kTileW, kWaveRows = 64 / kWaveCols, kWavesAcross = kTileW / kWaveCols;
-  const int lx = (w % kWavesAcross) * kWaveCols + (lane & (kWaveCols - 1));
-  const int lxo = lx * kUnit, ly = (w / kWavesAcross) * kWaveRows + lane / kWaveCols;
-#if GCP_TILE_SX == 4
+  // the lane's pixel in the tile: column lane & 15 (lxo: in pair units), row ly — 4 pixel rows per wave
+  const int lxo = (lane & 15) * kUnit, ly = w * 4 + (lane >> 4);
   const unsigned lane_bits = (1u << (lane & 15)) | (1u << (16 + ly));
-#else
-  const unsigned lane_bits = 1u << (lx & 31);
-#endif
   const int first = a.tile_start[tile], last = a.tile_start[tile + 1];
   const int nrounds = (last - first + kWalkStage - 1) / kWalkStage;
   float acc = (MODE == 0) ? 1.0f : 0.0f;
@@ -1292,32 +1207,23 @@ __global__ __launch_bounds__(kWalkThreads) void k_pairs_scan_boxes(const BlendAr
     const int cnt = min(kWalkStage, last - base);
     __syncthreads();
     if (w == 0) {  // wave 0 stages the round (a fifth wave staging one round ahead of the walkers: measured 6 % slower)
-      unsigned rm = 0u, cmask32 = 0u;
+      unsigned rm = 0u;
       if (lane < cnt) {
         const i64 g = a.tile_list[base + lane];
         Box b;
         load_box(a.start, a.end, g, a.W, a.H, b);
         const int wd = b.x1 - b.x0 + 1;
-        const int c0 = max(b.x0 - tile_x0, 0), c1 = min(b.x1 - tile_x0, kTileW - 1);
-        const int r0 = max(b.y0 - tile_y0, 0), r1 = min(b.y1 - tile_y0, kTileH - 1);
+        const int c0 = max(b.x0 - tile_x0, 0), c1 = min(b.x1 - tile_x0, kTile - 1);
+        const int r0 = max(b.y0 - tile_y0, 0), r1 = min(b.y1 - tile_y0, kTile - 1);
         const unsigned long long cm = (c1 >= c0) ? ((2ull << c1) - (1ull << c0)) : 0ull;
         rm = (r1 >= r0 && cm) ? ((2u << r1) - (1u << r0)) : 0u;
-        cmask32 = (unsigned)cm;
         // modulo 2^32: every pair of the list lies below 2^32 bytes (2^31 pairs when WIDE), whatever the tile's corner does
         const unsigned p0 = (unsigned)box_off[g] + (unsigned)(tile_y0 - b.y0) * (unsigned)wd + (unsigned)(tile_x0 - b.x0);
-#if GCP_TILE_SX == 4
         s_ent[lane] = make_int4((int)(p0 * (unsigned)kUnit), wd * kUnit, (int)((unsigned)cm | (rm << 16)), 0);
-#elif GCP_TILE_SX == 5
-        s_ent[lane] = make_int4((int)(p0 * (unsigned)kUnit), wd * kUnit, (int)(unsigned)cm, (int)rm);
-#else
-        s_ent[lane] = make_int4((int)(p0 * (unsigned)kUnit), wd * kUnit, (int)(unsigned)cm, (int)(unsigned)(cm >> 32));
-#endif
       }
 #pragma unroll
-      for (int w2 = 0; w2 < kWalkThreads / 64; ++w2) {
-        const bool rows_hit = ((rm >> (kWaveRows * (w2 / kWavesAcross))) & ((1u << kWaveRows) - 1u)) != 0u;
-        const bool cols_hit = !kWalkSuper || ((cmask32 >> (16 * (w2 % kWavesAcross))) & 0xffffu) != 0u;
-        const unsigned long long touched = __ballot(rows_hit && cols_hit);
+      for (int w2 = 0; w2 < 4; ++w2) {  // wave w2 walks pixel rows 4 w2 .. 4 w2 + 3
+        const unsigned long long touched = __ballot(((rm >> (4 * w2)) & 0xfu) != 0u);
         if (lane == 0) s_hits[w2] = touched;
       }
     }
@@ -1343,139 +1249,6 @@ __global__ __launch_bounds__(kWalkThreads) void k_pairs_scan_boxes(const BlendAr
     }
   }
 }
-
-#if GCP_WALK_DENSE
-// ---- measurement build: the DENSE walk on tiles of kTileW x kTileH pixels (<= 1024) --------------------------------------
-// One wave per tile; its lanes are laid over the PAIRS of an entry's box inside the tile, row-major, so that a box that is not
-// cut by the tile's left / right edge is read and written as ONE contiguous run across its rows (consecutive box rows are
-// adjacent in memory): with 64-pixel-wide tiles four boxes in five.  The pixels' running values live in LDS.
-struct DenseBatch {
-  bool in[kWalkBatch];
-  unsigned off[kWalkBatch];
-  int slot[kWalkBatch];
-  float v[kWalkBatch];
-};
-struct DenseCursor {
-  unsigned long long hits;
-  int k, it, nit;
-  __device__ __forceinline__ bool more() const { return hits != 0ull || (k >= 0 && it + 1 < nit); }
-};
-template <int MODE, bool WIDE>
-__device__ __forceinline__ void dense_load(DenseBatch& b, DenseCursor& c, const int4& rec, int lane, const float* __restrict__ x) {
-  constexpr int kUnit = WIDE ? 1 : 4;
-#pragma unroll
-  for (int u = 0; u < kWalkBatch; ++u) {
-    if (c.k >= 0 && c.it + 1 < c.nit) {
-      ++c.it;
-    } else {
-      if (MODE == 2) {
-        c.k = c.hits ? 63 - __builtin_clzll(c.hits) : -1;
-        c.hits &= ~(1ull << (c.k & 63));
-      } else {
-        c.k = c.hits ? __builtin_ctzll(c.hits) : -1;
-        c.hits &= c.hits - 1ull;
-      }
-      c.it = 0;
-      c.nit = c.k < 0 ? 0 : ((__builtin_amdgcn_readlane(rec.z, c.k & 63) >> 20) & 31);
-    }
-    const int ep = __builtin_amdgcn_readlane(rec.x, c.k & 63), ewd = __builtin_amdgcn_readlane(rec.y, c.k & 63);
-    const int geo = c.k < 0 ? 0 : __builtin_amdgcn_readlane(rec.z, c.k & 63);  // cw | pairs << 8 | parts << 20
-    const int iw = __builtin_amdgcn_readlane(rec.w, c.k & 63);                  // 65536 / cw rounded up | first pixel slot << 17
-    const int cw = geo & 255, tot = (geo >> 8) & 4095, inv = iw & 0x1ffff, sbase = (int)((unsigned)iw >> 17);
-    const int i = lane + 64 * c.it;
-    const int row = (int)(__umul24((unsigned)i, (unsigned)inv) >> 16);  // i / cw, exact for i < 1100 and cw <= 64
-    const int col = i - row * cw;
-    b.in[u] = i < tot;
-    const unsigned o = (unsigned)ep + (unsigned)row * (unsigned)ewd + (unsigned)(col * kUnit);
-    b.off[u] = b.in[u] ? o : 0u;
-    b.slot[u] = sbase + row * kTileW + col;
-    b.v[u] = WIDE ? x[b.off[u]] : *(const float*)((const char*)x + b.off[u]);
-  }
-}
-template <int MODE, bool WIDE, int OUT>
-__device__ __forceinline__ void dense_fold(const DenseBatch& b, float* __restrict__ out, float* __restrict__ acc_lds,
-                                           int* __restrict__ dropped, unsigned char* __restrict__ keep) {
-#pragma unroll
-  for (int u = 0; u < kWalkBatch; ++u) {
-    bool drop = false;
-    if (b.in[u]) {
-      float acc = acc_lds[b.slot[u]];
-      acc = (MODE == 0) ? acc * b.v[u] : acc + b.v[u];
-      acc_lds[b.slot[u]] = acc;
-      drop = acc == 0.0f;
-      const float res = (OUT != kWalkFinal) ? acc : (MODE == 0 ? acc / b.v[u] : acc - b.v[u]);
-      if (WIDE) out[b.off[u]] = res;
-      else *(float*)((char*)out + b.off[u]) = res;
-    }
-    if (OUT != kWalkInclusive) {
-      if (OUT == kWalkFinal && __ballot(drop) != 0ull) {
-        if (drop) keep[WIDE ? b.off[u] : (b.off[u] >> 2)] = 0;
-      }
-      walk_count_dropped<WIDE>(drop, b.off[u], dropped);
-    }
-  }
-}
-template <int MODE, bool WIDE, int OUT>
-__global__ __launch_bounds__(256) void k_pairs_walk_dense(const BlendArgs a, const int* __restrict__ box_off, const float* __restrict__ x,
-                                                          float* __restrict__ out, int* __restrict__ dropped,
-                                                          unsigned char* __restrict__ keep, int n_tiles, int n_blocks, int xcd_remap) {
-  constexpr int kPix = kTileW * kTileH;
-  static_assert(kPix <= 1024 && kTileW <= 64, "dense walk: tiles of at most 1024 pixels, 64 wide");
-  __shared__ float s_acc[4][kPix];
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int chunk = (int)sort_chunk(blockIdx.x, n_blocks, xcd_remap);
-  if (chunk < 0) return;
-  const int tile = 4 * chunk + w;
-  if (tile >= n_tiles) return;
-  const int first = a.tile_start[tile], n = a.tile_start[tile + 1] - first;
-  if (n <= 0) return;
-  float* const acc = s_acc[w];
-#pragma unroll
-  for (int j = 0; j < kPix / 64; ++j) acc[lane + 64 * j] = (MODE == 0) ? 1.0f : 0.0f;
-  const int tile_x0 = (tile % a.tiles_x) * kTileW, tile_y0 = (tile / a.tiles_x) * kTileH;
-  constexpr int kUnit = WIDE ? 1 : 4;
-  const int nrounds = (n + kWalkStage - 1) / kWalkStage;
-  for (int q0 = 0; q0 < nrounds; ++q0) {
-    const int q = (MODE == 2) ? (nrounds - 1 - q0) : q0;
-    const int base = first + q * kWalkStage;
-    const int cnt = min(kWalkStage, first + n - base);
-    int4 rec = make_int4(0, 0, 0, 0);
-    bool valid = false;
-    if (lane < cnt) {
-      const i64 g = a.tile_list[base + lane];
-      Box b;
-      load_box(a.start, a.end, g, a.W, a.H, b);
-      const int wd = b.x1 - b.x0 + 1;
-      const int c0 = max(b.x0 - tile_x0, 0), c1 = min(b.x1 - tile_x0, kTileW - 1);
-      const int r0 = max(b.y0 - tile_y0, 0), r1 = min(b.y1 - tile_y0, kTileH - 1);
-      const int cw = c1 - c0 + 1, ch = r1 - r0 + 1;
-      valid = cw > 0 && ch > 0;
-      if (valid) {
-        const unsigned p0 = (unsigned)box_off[g] + (unsigned)(tile_y0 + r0 - b.y0) * (unsigned)wd + (unsigned)(tile_x0 + c0 - b.x0);
-        const int tot = cw * ch;
-        rec = make_int4((int)(p0 * (unsigned)kUnit), wd * kUnit, cw | (tot << 8) | (((tot + 63) >> 6) << 20),
-                        (int)((65535u / (unsigned)cw + 1u) | ((unsigned)(r0 * kTileW + c0) << 17)));
-      }
-    }
-    DenseCursor c;
-    c.hits = __ballot(valid);
-    c.k = -1; c.it = 0; c.nit = 0;
-    if (c.hits) {
-      DenseBatch A, B;
-      dense_load<MODE, WIDE>(A, c, rec, lane, x);
-      for (;;) {
-        if (!c.more()) { dense_fold<MODE, WIDE, OUT>(A, out, acc, dropped, keep); break; }
-        dense_load<MODE, WIDE>(B, c, rec, lane, x);
-        dense_fold<MODE, WIDE, OUT>(A, out, acc, dropped, keep);
-        if (!c.more()) { dense_fold<MODE, WIDE, OUT>(B, out, acc, dropped, keep); break; }
-        dense_load<MODE, WIDE>(A, c, rec, lane, x);
-        dense_fold<MODE, WIDE, OUT>(B, out, acc, dropped, keep);
-      }
-    }
-  }
-}
-#endif  // GCP_WALK_DENSE
 
 // Gaussian-major rect list (reference: Utilities.make_rect_points_parallel, uitility.py:336-366, called by
 // _create_rects, gs_model.py:480-482): pair i of Gaussian g is pixel (x0 + i % w, y0 + i / w) of its box.
@@ -1574,9 +1347,6 @@ __global__ __launch_bounds__(256) void k_rects_key_range(const int* rects, i64 n
 // the tile's kept count.  WRITE = true: every kept element's rank = tile offset (exclusive scan of the counts) + kept
 // elements before it in the tile (per-lane popcounts -> wave prefix in DPP -> 4 LDS words), its value written to that
 // slot — neighbouring lanes write neighbouring slots — and the mask as one packed word per lane.
-#ifndef GCP_COMPACT_X4
-#define GCP_COMPACT_X4 1
-#endif
 constexpr int kCompactTile = 1 << kDropTileLog2;
 template <bool VEC, bool WRITE>
 __global__ __launch_bounds__(256) void k_compact(const float* __restrict__ incl, const float* __restrict__ self, i64 n, int mode,
@@ -1634,7 +1404,6 @@ __global__ __launch_bounds__(256) void k_compact(const float* __restrict__ incl,
   for (int r = 0; r < 4; ++r) {
     const i64 p = base + r * 256 + lane * 4;
     int o = woff + before[r];
-#if GCP_COMPACT_X4
     if (m[r] == 0xfu) {
       // all four kept (every lane of a stretch that drops nothing): one 16-byte store at a 4-byte-aligned slot — a wave
       // then writes 1 KB contiguous with one instruction instead of four strided ones
@@ -1645,9 +1414,7 @@ __global__ __launch_bounds__(256) void k_compact(const float* __restrict__ incl,
       q.z = mode == 0 ? v[r][2] / x[r][2] : v[r][2] - x[r][2];
       q.w = mode == 0 ? v[r][3] / x[r][3] : v[r][3] - x[r][3];
       *reinterpret_cast<float4_u*>(values + o) = q;
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if ((m[r] >> k) & 1u) {
@@ -2034,7 +1801,7 @@ static int sort_impl(const unsigned* keys_in, bool rects, int64_t n, int32_t key
   if (n == 0) return GCP_OK;
   if (!keys_in || !keys_out || !index_out || !ws) return GCP_ERR_INVALID_ARGUMENT;
   if (ws_bytes < gcp_sort_workspace_bytes(n)) return GCP_ERR_WORKSPACE;
-  static const int xcd_remap = [] { const char* e = getenv("GCP_SORT_XCD"); return (e && *e) ? atoi(e) : 1; }();
+  constexpr int xcd_remap = 1;  // XCD x takes the x-th contiguous eighth of the chunks (sort_chunk)
   const i64 nblk = (n + kBigChunk - 1) / kBigChunk;
   // chunks per block: as many as kSortSub, but keep a few thousand blocks for the 1024 block slots of the chip
   int sub = (int)(nblk / 2048);
@@ -2184,7 +1951,7 @@ static int walk_impl(const int32_t* start_xy, const int32_t* end_xy, int64_t n_g
   // stripes of one tile row dealt round-robin to the XCDs (walk_tile): as fast as contiguous bands on a scene that fills the
   // image evenly (0.65 against 0.64 ms at cfg3), and 18 % / 43 % faster where the Gaussians crowd the middle (sigma = extent / 4,
   // / 8: the bands of the crowded region worked while the others idled) — profiles/r04_walk_experiments.md
-  static const int xcd_remap = [] { const char* e = getenv("GCP_WALK_XCD"); return (e && *e) ? atoi(e) : 2; }();
+  constexpr int xcd_remap = 2;
   // pair positions as 32-bit byte offsets while the list is no longer than 2^30 pairs (GCP_WALK_WIDE=1 forces the other form)
   const char* fw = getenv("GCP_WALK_WIDE");  // read per call: the tests switch it inside one process
   const bool wide = (fw && *fw && atoi(fw) != 0) || n_pairs > (1LL << 30);
@@ -2193,16 +1960,9 @@ static int walk_impl(const int32_t* start_xy, const int32_t* end_xy, int64_t n_g
   if ((int64_t)width + 1 >= (wide ? (1LL << 24) : (1LL << 22))) return GCP_ERR_INVALID_ARGUMENT;
   const int out_mode = keep ? kWalkFinal : (dropped_per_tile ? kWalkCount : kWalkInclusive);
   const int n_tiles = tg.tx * tg.ty;
-  const dim3 grid(walk_grid(n_tiles, tg.tx, xcd_remap)), block(kWalkThreads);
-#if GCP_WALK_DENSE
-  const int n_blocks = (n_tiles + 3) / 4;
-  const dim3 dgrid(sort_grid(n_blocks, xcd_remap));
-#define GCP_WALK(M, W_, O_) \
-  hipLaunchKernelGGL((k_pairs_walk_dense<M, W_, O_>), dgrid, dim3(256), 0, stream, a, box_off, x, out, dropped_per_tile, keep, n_tiles, n_blocks, xcd_remap)
-#else
+  const dim3 grid(walk_grid(n_tiles, tg.tx, xcd_remap)), block(256);
 #define GCP_WALK(M, W_, O_) \
   hipLaunchKernelGGL((k_pairs_scan_boxes<M, W_, O_>), grid, block, 0, stream, a, box_off, x, out, dropped_per_tile, keep, n_tiles, xcd_remap)
-#endif
 #define GCP_WALK_OUT(M, W_)                                  \
   do {                                                       \
     if (out_mode == kWalkFinal) GCP_WALK(M, W_, kWalkFinal); \

@@ -74,18 +74,9 @@ enum : int { M_CUMPROD_FWD = 0, M_CUMSUM_FWD = 1, M_CUMPROD_BWD = 2, M_CUMSUM_RE
 
 constexpr int kThreads = 256;      // 4 waves
 constexpr int kWaves = 4;
-#ifndef GCP_ROWS
-#define GCP_ROWS 4
-#endif
-#ifndef GCP_XCD_REMAP_DEFAULT
-#define GCP_XCD_REMAP_DEFAULT 1
-#endif
-constexpr int kRows = GCP_ROWS;    // 16-byte vectors per lane per array
+constexpr int kRows = 4;           // 16-byte vectors per lane per array
 constexpr int kTile = 1024 * kRows;
-#ifndef GCP_LB_BATCH
-#define GCP_LB_BATCH 5
-#endif
-constexpr int kLbBatch = GCP_LB_BATCH;  // look-back chunks fetched per dependent round trip after the first
+constexpr int kLbBatch = 5;        // look-back chunks fetched per dependent round trip after the first
 constexpr int kLbChunks = ((kTile / 256 - 1) / kLbBatch) * kLbBatch + 1;  // window in 256-element chunks (16 = one tile at kRows 4)
 constexpr int kFixBlocks = 256;     // upper bound of the fallback kernel's grid (two-pass mode)
 constexpr int kFixBlocksQuiet = 32; // ... when the descriptor tree is on and the kernel normally finds nothing to do
@@ -105,17 +96,10 @@ constexpr unsigned kDOpen = 1u;        // the aggregate is relative to the tile'
 constexpr unsigned kDUnresolved = 2u;  // the tile's leading elements still lack their carry (the fallback kernel's work list)
 constexpr unsigned kDValid = 1u << 15; // published in this launch (the set was cleared before)
 constexpr unsigned kDTree = 1u << 16;  // the tile took its carry from the block tree (introspection; level 0 only)
-#ifndef GCP_XCD_CHUNK
-#define GCP_XCD_CHUNK 32
-#endif
 constexpr int kLevels = 4;          // radix-64 block tree over the tiles: 64^4 tiles = 6.9e10 elements
-constexpr int kXcdChunk = GCP_XCD_CHUNK;  // consecutive tiles one XCD takes before the next XCD's run starts
-#ifndef GCP_DESC_WAIT_US
-#define GCP_DESC_WAIT_US 200
-#endif
-#ifndef GCP_LB_EARLY_EXIT
-#define GCP_LB_EARLY_EXIT 1      // leave the raw look-back after its first chunk when wave 0's whole share is head-less (§3.1 of DESIGN.md)
-#endif
+constexpr int kXcdChunk = 32;       // consecutive tiles one XCD takes before the next XCD's run starts (logical_tile)
+constexpr int kXcdChunkIndexed = 128;  // ... in the INDEXED scans
+constexpr int kDescWaitUs = 200;    // default patience of the descriptor walk (gcp_set_lookback_wait_us)
 
 static_assert(kLbChunks * 256 == kTile, "the raw look-back window is exactly the previous tile (the descriptor walk starts at the tile before it)");
 static_assert((kLbChunks - 1) % kLbBatch == 0, "chunks after the first are fetched kLbBatch at a time");
@@ -192,15 +176,9 @@ __device__ __forceinline__ float wave_reduce(float v) {
 // Cache policy of the streaming accesses (A/B on cfg3, one process, interleaved): non-temporal STORES
 // +1.8 % (forward) / +3.9 % (backward).  Non-temporal LOADS of everything: -7 % with the look-back loads
 // included, +1.7 % forward / -3.5 % backward with only the tile loads (and -15 % on cache-resident cfg2):
-// the look-back re-reads the END of the neighbouring tile and wants it cached.  Mode 2 — non-temporal for
-// all waves but the last one in scan order, plus `param` in the backward, which no look-back touches —
-// is neutral on the forward and cfg2 and +1.3 % on the backward.
-#ifndef GCP_NT_LOAD
-#define GCP_NT_LOAD 2
-#endif
-#ifndef GCP_NT_STORE
-#define GCP_NT_STORE 1
-#endif
+// the look-back re-reads the END of the neighbouring tile and wants it cached.  So the aligned stores are
+// non-temporal, and so are the tile loads of all waves but the last one in scan order, plus `param` in the
+// backward, which no look-back touches: neutral on the forward and cfg2 and +1.3 % on the backward.
 template <bool ALIGNED, bool NT = false>
 __device__ __forceinline__ float4_t ld4(const float* p) {
   if (ALIGNED) {
@@ -222,8 +200,7 @@ __device__ __forceinline__ int4_t ld4(const int* p) {
 template <bool ALIGNED>
 __device__ __forceinline__ void st4(float* p, float4_t v) {
   if (ALIGNED) {
-    if (GCP_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<float4_t*>(p));
-    else *reinterpret_cast<float4_t*>(p) = v;
+    __builtin_nontemporal_store(v, reinterpret_cast<float4_t*>(p));
     return;
   }
   p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
@@ -385,9 +362,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
 
   // ---- issue all loads of this lane ------------------------------------
   // Streaming (non-temporal) loads are faster for bytes nobody reads again, but the END of a tile (scan
-  // order) is what the next tile's look-back re-reads and must stay cached: GCP_NT_LOAD 0 = never,
-  // 1 = all tile loads, 2 = all waves but the last one in scan order.
-  const bool nt_main = (GCP_NT_LOAD == 1) || (GCP_NT_LOAD == 2 && w < kWaves - 1);
+  // order) is what the next tile's look-back re-reads and must stay cached: the last wave loads through the cache.
+  const bool nt_main = w < kWaves - 1;
   float4_t v[kRows];
   int4_t kk[kRows];
   float4_t xp[BWD ? kRows : 1];
@@ -428,7 +404,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
           v[r] = ld4<ALIGNED>(a.in0 + p0[r]);
         }
       }
-      if constexpr (BWD) xp[r] = ld4<ALIGNED, (GCP_NT_LOAD != 0)>(a.in0 + p0[r]);  // param is never re-read by a look-back
+      if constexpr (BWD) xp[r] = ld4<ALIGNED, true>(a.in0 + p0[r]);  // param is never re-read by a look-back
     } else {
       if constexpr (BWD) {
         const float4_t g = ld4_guard(a.in2, p0[r], n, 0.0f);
@@ -624,8 +600,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       bool done = process(lbv, lbk, lbp, 0);
       // A group that already spans the 256 elements behind the tile AND this wave's whole 1024-element share is long:
       // stop reading raw inputs (up to three more dependent round trips that would most likely end at the window's
-      // edge) and take the carry from the descriptor tree.  A data-determined rule, so still deterministic.
-      bool wave_headless = GCP_LB_EARLY_EXIT != 0;
+      // edge) and take the carry from the descriptor tree (§3.1 of DESIGN.md).  A data-determined rule, so still deterministic.
+      bool wave_headless = true;
 #pragma unroll
       for (int r = 0; r < kRows; ++r) wave_headless = wave_headless && (hmask[r] == 0ull);
       for (int j = 1; !done && !wave_headless && j < kLbChunks; j += kLbBatch) {
@@ -1203,11 +1179,6 @@ int check_group_ids_impl(const int* inv, i64 n, i64 n_groups, int64_t* n_bad, hi
   return h ? GCP_ERR_INVALID_ARGUMENT : GCP_OK;
 }
 
-int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return (s && *s) ? atoi(s) : dflt;
-}
-
 template <int MODE>
 int launch_scan(const float* in0, const float* in1, const float* in2, const int* key, float* out,
                 i64 n, void* ws, size_t ws_bytes, void* stream_, const float* carry = nullptr, const int* index = nullptr,
@@ -1250,12 +1221,13 @@ int launch_scan(const float* in0, const float* in1, const float* in2, const int*
   a.hdr = (unsigned*)p; p += kWsHeaderBytes;
   a.desc_sets = (unsigned long long*)p;
   ws_levels(n, a.lvl_off);
-  static const int xcd_remap = env_int("GCP_XCD_REMAP", GCP_XCD_REMAP_DEFAULT);
-  static const int chunk_lg = [] { int l = 0; while ((1 << l) < kXcdChunk) ++l; return l; }();
-  static const int chunk_lg_indexed = env_int("GCP_XCD_CHUNK_INDEXED_LOG2", 7);
-  a.xcd_remap = xcd_remap ? 1 + (index ? chunk_lg_indexed : chunk_lg) : 0;
+  a.xcd_remap = 1 + __builtin_ctz(index ? kXcdChunkIndexed : kXcdChunk);
   long long us = g_patience_us.load(std::memory_order_relaxed);
-  if (us == -2) { us = env_int("GCP_DESC_WAIT_US", GCP_DESC_WAIT_US); g_patience_us.store(us, std::memory_order_relaxed); }
+  if (us == -2) {
+    const char* s = getenv("GCP_DESC_WAIT_US");
+    us = (s && *s) ? atoi(s) : kDescWaitUs;
+    g_patience_us.store(us, std::memory_order_relaxed);
+  }
   a.patience = us < 0 ? -1 : us * 100;  // wall_clock64() counts at 100 MHz
 
   uintptr_t al = (uintptr_t)in0 | (uintptr_t)key | (uintptr_t)out;

@@ -2,6 +2,8 @@
 (cdna_hip_programming.md §5.4 rule 24).  Calls the C ABI directly through ctypes.
 
   python tools/ab_bench.py --config cfg3 --rounds 7 --iters 10 variants/a.so variants/b.so
+
+variants/<name>.so: lib/libgrouped_cumprod_hip.so as built from another checkout.
 """
 import argparse
 import ctypes

@@ -1,4 +1,5 @@
-# same-box A/B of the walk on clustered scenes over library variants:   gpurun -- bash tools/clustered_ab.sh wb16 ...
+# same-box A/B of the walk on clustered scenes over variants/<name>.so (the library built from another checkout):
+#   bash tools/clustered_ab.sh <name> ...
 set -e
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 mkdir -p gpurun_out/clustered_ab

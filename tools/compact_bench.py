@@ -1,6 +1,8 @@
 """compact_finish alone at a BASELINE scene size, with and without dropped rows: A/B runs of library variants.
 
-  GCP_LIBRARY=variants/x.so python tools/compact_bench.py [cfg3] [--iters 10]
+  GCP_LIBRARY=variants/<name>.so python tools/compact_bench.py [cfg3] [--iters 10]
+
+variants/<name>.so: lib/libgrouped_cumprod_hip.so as built from another checkout.
 """
 import json
 import os

@@ -1,4 +1,4 @@
-# same-box A/B of the cut over library variants:   gpurun -- bash tools/cut_ab.sh cut_base ...
+# same-box A/B of the cut over variants/<name>.so (the library built from another checkout):   bash tools/cut_ab.sh <name> ...
 set -e
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 export TMPDIR=/tmp

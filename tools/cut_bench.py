@@ -1,7 +1,9 @@
 """rects_to_boxes (the rect list cut back into boxes) alone, at a BASELINE scene size, from the int32 and the int64 list:
 A/B runs of library variants.
 
-  GCP_LIBRARY=variants/x.so python tools/cut_bench.py [cfg3] [--iters 10]
+  GCP_LIBRARY=variants/<name>.so python tools/cut_bench.py [cfg3] [--iters 10]
+
+variants/<name>.so: lib/libgrouped_cumprod_hip.so as built from another checkout.
 """
 import json
 import os

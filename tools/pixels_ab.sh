@@ -1,4 +1,5 @@
-# same-box A/B of csrc/gcp_pixels.hip over library variants:   gpurun -- bash tools/pixels_ab.sh px_nolook px_fwd
+# same-box A/B of csrc/gcp_pixels.hip over variants/<name>.so (the library built from another checkout):
+#   bash tools/pixels_ab.sh <name> ...
 set -e
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 mkdir -p gpurun_out/pixels_ab

@@ -1,6 +1,8 @@
 """Tile-list walk (k_pairs_scan_boxes) alone, at a BASELINE scene size: A/B runs of library variants.
 
-  GCP_LIBRARY=variants/walk8.so python tools/walk_bench.py [cfg3] [--iters 10]
+  GCP_LIBRARY=variants/<name>.so python tools/walk_bench.py [cfg3] [--iters 10]
+
+variants/<name>.so: lib/libgrouped_cumprod_hip.so as built from another checkout.
 """
 import json
 import os

@@ -1,5 +1,5 @@
 # HBM-side traffic of the tile-list walk (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes) for the product library
-# and any variants (tools/build_variant.py):   gpurun -- bash tools/walk_traffic.sh walk64 walksuper
+# and any variants/<name>.so (the library built from another checkout):   bash tools/walk_traffic.sh <name> ...
 set -e
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 export TMPDIR=/tmp
