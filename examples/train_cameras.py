@@ -7,6 +7,7 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
 
     python examples/train_cameras.py                         # synthetic scene (the default; runs anywhere)
     python examples/train_cameras.py --colmap DIR            # DIR/sparse/0/{cameras,images,points3D}.bin + DIR/images/
+    python examples/train_cameras.py --background random     # render over a random colour per step (or "1,1,1": white)
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -26,7 +27,9 @@ from simplegaussiansplat_tk71_amd import gs_model as gm  # noqa: E402
 from simplegaussiansplat_tk71_amd.synthetic import ring_cameras  # noqa: E402
 
 
-def synthetic_scene(n_gauss, n_cam, width, height, seed, device):
+def synthetic_scene(n_gauss, n_cam, width, height, seed, device, with_alpha=False):
+    """-> (start, P, K, wh, targets) [+ the targets' alpha maps (n_cam, 1, H, W) with_alpha: to composite them over the
+    background a step renders on]"""
     g = torch.Generator().manual_seed(seed)
     truth = {
         "mean": 0.6 * torch.randn(n_gauss, 3, generator=g),
@@ -42,9 +45,14 @@ def synthetic_scene(n_gauss, n_cam, width, height, seed, device):
     hidden = gm.GS_model_with_param(truth["mean"], truth["variance_q"], truth["variance_scale"], truth["opacity"])
     with torch.no_grad():
         hidden.color.copy_(color.to(device))
-        targets = torch.cat([hidden(P[i:i + 1], K[i:i + 1], wh[i:i + 1], ["t"])[0] for i in range(n_cam)]).clamp(0, 1)
+        if with_alpha:
+            shots = [hidden.render(P[i:i + 1], K[i:i + 1], wh[i:i + 1]) for i in range(n_cam)]
+            targets = torch.cat([s[0] for s in shots]).clamp(0, 1)
+            alphas = torch.cat([s[2] for s in shots])
+        else:
+            targets = torch.cat([hidden(P[i:i + 1], K[i:i + 1], wh[i:i + 1], ["t"])[0] for i in range(n_cam)]).clamp(0, 1)
     start = truth["mean"] + 0.02 * torch.randn(n_gauss, 3, generator=g).to(device)  # a noisy point cloud
-    return start, P, K, wh, targets
+    return (start, P, K, wh, targets, alphas) if with_alpha else (start, P, K, wh, targets)
 
 
 def load_colmap(root, device):
@@ -59,9 +67,14 @@ def load_colmap(root, device):
 
 def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2, opacity_init=0.1, neighbours=3,
           densify_from_iter=500, densify_until_iter=15000, densification_interval=100, opacity_reset_interval=3000,
-          reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1):
+          reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
-    `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads)."""
+    `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
+    `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
+    generator: the same on every rank); the images are then rendered over it (GS_model_with_param.render) and, where
+    `target_alpha` (B, 1, H, W) is given, the targets composited over it too."""
+    if isinstance(background, str) and background != "random":
+        raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
     torch.manual_seed(seed)  # densification draws samples: every rank must draw the same ones
     n = start.shape[0]
@@ -80,8 +93,18 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             idx = order[b:b + batch_size].to(dev)
             mine = idx[rank::world]
             if mine.numel():
-                images, kept, grad_iter = model(P[mine], K[mine], wh[mine], mine.tolist())
-                loss = gm.splat_loss(images, targets[torch.tensor(kept, device=dev)], loss_lamda) * (mine.numel() / idx.numel())
+                if background is None:
+                    images, kept, grad_iter = model(P[mine], K[mine], wh[mine], mine.tolist())
+                    target = targets[torch.tensor(kept, device=dev)]
+                else:
+                    bg = torch.rand(3, device=dev) if isinstance(background, str) else torch.as_tensor(background, dtype=torch.float32,
+                                                                                                          device=dev)
+                    images, _, _, kept, grad_iter = model.render(P[mine], K[mine], wh[mine], background=bg, image_sample=mine.tolist())
+                    sel = torch.tensor(kept, device=dev)
+                    target = targets[sel]
+                    if target_alpha is not None:
+                        target = target + (1 - target_alpha[sel]) * bg[None, :, None, None]
+                loss = gm.splat_loss(images, target, loss_lamda) * (mine.numel() / idx.numel())
                 loss.backward()
             else:  # more ranks than cameras in this batch
                 loss, grad_iter = torch.zeros((), device=dev), torch.zeros(model.mean.shape[0], dtype=torch.bool, device=dev)
@@ -123,7 +146,9 @@ if __name__ == "__main__":
     ap.add_argument("--iterations", type=int, default=400)
     ap.add_argument("--densify-from", type=int, default=500)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend under torchrun (nccl = RCCL; gloo to rehearse on one GPU)")
+    ap.add_argument("--background", default=None, help='"random" (a colour per step) or "r,g,b"; default: black')
     a = ap.parse_args()
+    background = a.background if a.background in (None, "random") else tuple(float(v) for v in a.background.split(","))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(device)
@@ -132,12 +157,15 @@ if __name__ == "__main__":
             torch.distributed.init_process_group("nccl", device_id=device)
         else:
             torch.distributed.init_process_group(a.backend)
+    alphas = None
     if a.colmap:
         start, P, K, wh, targets = load_colmap(a.colmap, device)
+    elif background is not None:
+        start, P, K, wh, targets, alphas = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device, with_alpha=True)
     else:
         start, P, K, wh, targets = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device)
     _, losses = train(start, P, K, wh, targets, iterations=a.iterations, densify_from_iter=a.densify_from, rank=rank, world=world,
-                      log=print if rank == 0 else (lambda *_: None))
+                      log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

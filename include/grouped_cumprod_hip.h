@@ -289,6 +289,33 @@ int gcp_blend_backward(const int32_t* start_xy, const int32_t* end_xy, const flo
                        float* grad_vinv, float* grad_opacity, float* grad_l, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* f1 with depth, alpha and a background colour: the same blend, the same bins and checkpoints, and per pixel p of the
+ * (H+1) x (W+1) frame, with w_k = T_k o_k g_k the colour weights (pairs whose inclusive product is exactly 0 have
+ * w_k = 0) and T_N the transmittance behind the pixel's whole list:
+ *   depth_map(p) = sum_k w_k z_k       (z = depth [N], e.g. the camera-space depth; NOT divided by alpha)
+ *   alpha_map(p) = 1 - T_N(p)
+ *   image(p)     = sum_k w_k l_k + T_N(p) * background   (background: float[3] in DEVICE memory, or NULL = black, in which
+ *                                                         case the image is gcp_blend_forward's bit for bit)
+ * t_ckpt as for gcp_blend_forward (NULL: no backward).  The backward returns the exact derivatives of these definitions
+ * for kept pairs (dropped pairs get zero) of <image, grad_image> + <depth_map, grad_depth_map> + <alpha_map,
+ * grad_alpha_map>: grad_depth_map / grad_alpha_map may be NULL (zero); grad_depth [N] receives dL/dz; grad_background
+ * (float[3], or NULL: not computed) sum_p grad_image(p) T_N(p), summed in a fixed order (no atomics).  With
+ * n_gauss == 0 only grad_background is written.  ws: gcp_blend_backward_depth_workspace_bytes(K, width, height). */
+int gcp_blend_forward_depth(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy,
+                            const float* vinv, const float* opacity, const float* l_d, const float* depth,
+                            const float* background, int64_t n_gauss, int32_t width, int32_t height,
+                            const int32_t* tile_start, const int32_t* tile_list, float* image,
+                            float* depth_map, float* alpha_map, float* t_ckpt, void* stream);
+size_t gcp_blend_backward_depth_workspace_bytes(int64_t n_tile_pairs, int32_t width, int32_t height);
+int gcp_blend_backward_depth(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy,
+                             const float* vinv, const float* opacity, const float* l_d, const float* depth,
+                             const float* background, int64_t n_gauss, int32_t width, int32_t height,
+                             const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start,
+                             const int32_t* tile_list, const float* t_ckpt, const float* grad_image,
+                             const float* grad_depth_map, const float* grad_alpha_map, float* grad_mean,
+                             float* grad_vinv, float* grad_opacity, float* grad_l, float* grad_depth,
+                             float* grad_background, void* ws, size_t ws_bytes, void* stream);
+
 /* Stable sort of n uint32 keys that also returns the permutation: keys_out[i] = keys_in[index_out[i]], equal
  * keys keep their input order — what the reference asks of torch.sort for its pixel keys (gs_model.py:546-547;
  * depth order inside a pixel rides on that stability).  LSD radix sort over the low `key_bits` bits (8 per
@@ -506,7 +533,10 @@ int gcp_pixel_lists_fill(const int32_t* start_xy, const int32_t* end_xy, int64_t
  * Gaussians without the kept count ever being read back: the culled ones follow the kept ones with an empty box (binned
  * into no tile, blended nowhere, zero gradients) — the capture-safe form; keep = NULL: the first n_kept entries only.
  * gcp_project_backward: gradients of (mean, quaternion, log scale, opacity logit, SH coefficients), n_gauss rows
- * each, all rows written (zeros where row_of < 0), from those of (Sigma'^-1, opacity, l_d) in list order. */
+ * each, all rows written (zeros where row_of < 0), from those of (Sigma'^-1, opacity, l_d) in list order.
+ * gcp_project_gather_depth / gcp_project_backward_depth: the same plus each Gaussian's camera-space depth z (the
+ * positive depth the sort key holds; 0 for a culled entry of the capture-safe form) in list order, and its gradient
+ * grad_depth [n_kept] (dz/dmean = row 2 of [R|t]). */
 int gcp_project_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
                         const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
                         int32_t n_basis, int32_t width, int32_t height, float box_clamp, float* record, int32_t* sort_key,
@@ -519,6 +549,14 @@ int gcp_project_backward(const float* mean, const float* quat_xyzw, const float*
                          int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                          const float* grad_l_d, float* grad_mean, float* grad_quat, float* grad_log_scale,
                          float* grad_opacity_logit, float* grad_sh_coeff, void* stream);
+int gcp_project_gather_depth(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy,
+                             int32_t* mean_xy, int64_t* boxsize, float* vinv, float* alpha, float* l_d, float* depth,
+                             int64_t* index, int32_t* row_of, const uint8_t* keep /* may be NULL */, void* stream);
+int gcp_project_backward_depth(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                               const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                               int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                               const float* grad_l_d, const float* grad_depth, float* grad_mean, float* grad_quat,
+                               float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream);
 
 /* ---- the caller's training loss, fused ---------------------------------------------------
  * (1 - lambda) * mean|a - b| + lambda * (1 - mean SSIM(a, b)) of gs_control.py:180-182 (kornia.metrics.ssim with an

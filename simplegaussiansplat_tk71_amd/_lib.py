@@ -71,6 +71,9 @@ SIGNATURES = {
         ctypes.c_int,
         [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 8 + [_c_void_p, _sz, _c_void_p],
     ),
+    "gcp_blend_forward_depth": (ctypes.c_int, [_c_void_p] * 8 + [_i64, _i32, _i32] + [_c_void_p] * 7),
+    "gcp_blend_backward_depth_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gcp_blend_backward_depth": (ctypes.c_int, [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 13 + [_sz, _c_void_p]),
     "gcp_gather_f32": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p]),
     "gcp_unsort_finish": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i32, _c_void_p]),
     "gcp_sort_workspace_bytes": (_sz, [_i64]),
@@ -109,6 +112,8 @@ SIGNATURES = {
                             + [_c_void_p] * 5),
     "gcp_ssim_l1_backward": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "gcp_project_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 10),
+    "gcp_project_gather_depth": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
+    "gcp_project_backward_depth": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 11),
 }
 
 ABI_VERSION = 4

@@ -181,7 +181,7 @@ __device__ __forceinline__ void box_halfsize(float a, float b, float c, float& h
 __device__ __forceinline__ int trunc_i32(float v) { return (int)v; }
 
 // Per Gaussian, one 64-byte record (what the gather reads back in one piece), the sort key of its depth and the cull flag.
-//   record words: 0-3 box x0 y0 x1 y1 | 4-5 pixel mean | 6-9 Sigma'^-1 | 10 opacity | 11-13 colour | 14-15 unused
+//   record words: 0-3 box x0 y0 x1 y1 | 4-5 pixel mean | 6-9 Sigma'^-1 | 10 opacity | 11-13 colour | 14 camera depth | 15 unused
 
 __global__ __launch_bounds__(kThreads) void k_project_fwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
@@ -235,15 +235,17 @@ __global__ __launch_bounds__(kThreads) void k_project_fwd(
     rec[0] = make_float4(__int_as_float(x0), __int_as_float(y0), __int_as_float(x1), __int_as_float(y1));
     rec[1] = make_float4(__int_as_float(mx), __int_as_float(my), p.d / p.det, -p.b / p.det);
     rec[2] = make_float4(-p.c / p.det, p.a / p.det, alpha, l[0]);
-    rec[3] = make_float4(l[1], l[2], 0.f, 0.f);
+    rec[3] = make_float4(l[1], l[2], p.t[2], 0.f);
   }
 }
 
-// Row r of the depth-ordered list is Gaussian perm[r]: unpack its record into the Function's argument arrays.
-__global__ __launch_bounds__(kThreads) void k_project_gather(
+// Row r of the depth-ordered list is Gaussian perm[r]: unpack its record into the Function's argument arrays (DEPTH: and its
+// camera depth, 0 for a culled one).
+template <bool DEPTH>
+__device__ __forceinline__ void project_gather(
     const float4* __restrict__ record, const int* __restrict__ perm, i64 m, int* __restrict__ start_xy,
     int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
-    float* __restrict__ alpha, float* __restrict__ l_d, i64* __restrict__ index, int* __restrict__ row_of,
+    float* __restrict__ alpha, float* __restrict__ l_d, float* __restrict__ depth, i64* __restrict__ index, int* __restrict__ row_of,
     const unsigned char* __restrict__ keep) {
   for (i64 r = (i64)blockIdx.x * kThreads + threadIdx.x; r < m; r += (i64)gridDim.x * kThreads) {
     const int i = perm[r];
@@ -261,20 +263,38 @@ __global__ __launch_bounds__(kThreads) void k_project_gather(
     reinterpret_cast<float4*>(vinv)[r] = make_float4(b.z, b.w, c.x, c.y);
     alpha[r] = c.z;
     l_d[3 * r] = c.w, l_d[3 * r + 1] = d.x, l_d[3 * r + 2] = d.y;
+    if (DEPTH) depth[r] = culled ? 0.f : d.z;
     index[r] = i;
     if (!culled) row_of[i] = (int)r;
   }
 }
 
+__global__ __launch_bounds__(kThreads) void k_project_gather(
+    const float4* __restrict__ record, const int* __restrict__ perm, i64 m, int* __restrict__ start_xy,
+    int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
+    float* __restrict__ alpha, float* __restrict__ l_d, i64* __restrict__ index, int* __restrict__ row_of,
+    const unsigned char* __restrict__ keep) {
+  project_gather<false>(record, perm, m, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, nullptr, index, row_of, keep);
+}
+
+__global__ __launch_bounds__(kThreads) void k_project_gather_depth(
+    const float4* __restrict__ record, const int* __restrict__ perm, i64 m, int* __restrict__ start_xy,
+    int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
+    float* __restrict__ alpha, float* __restrict__ l_d, float* __restrict__ depth, i64* __restrict__ index, int* __restrict__ row_of,
+    const unsigned char* __restrict__ keep) {
+  project_gather<true>(record, perm, m, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, depth, index, row_of, keep);
+}
+
 // One thread per Gaussian, in the Gaussians' own order (coalesced parameter reads and gradient writes); the only
 // scattered reads are the 8 upstream gradient words of its row `row_of[i]` in the depth-ordered list.  Culled
 // Gaussians (row -1) get zeros: every gradient row is written, nothing needs clearing first.
-__global__ __launch_bounds__(kThreads) void k_project_bwd(
+template <bool DEPTH>
+__device__ __forceinline__ void project_bwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
     const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
     const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
-    float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
+    const float* __restrict__ g_depth, float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
     float* __restrict__ grad_opacity, float* __restrict__ grad_color) {
   // parameter rows come in and gradient rows go out through LDS as contiguous runs: straight from / to registers they are
   // 37 + 38 four-byte accesses per thread, 12-108 bytes apart (gradient rows direct: 365 us per 10^6 Gaussians; staged: 140)
@@ -389,6 +409,7 @@ __global__ __launch_bounds__(kThreads) void k_project_bwd(
       if (p.t[2] > 1e-2f)
         gt[2] += gJ[0] * (-fx * iz2) + gJ[2] * (2.f * fx * p.t[0] * iz3) + gJ[4] * (-fy * iz2) + gJ[5] * (2.f * fy * p.t[1] * iz3);
     }
+    if (DEPTH) gt[2] += g_depth[r];  // the depth the blend weighted is t[2]
     // t = W m + t0  ->  dL/dm = W^T dL/dt
 #pragma unroll
     for (int k = 0; k < 3; ++k) lm[k] = (cam.P[k] * gt[0] + cam.P[4 + k] * gt[1]) + cam.P[8 + k] * gt[2];
@@ -449,6 +470,28 @@ __global__ __launch_bounds__(kThreads) void k_project_bwd(
   }
 }
 
+__global__ __launch_bounds__(kThreads) void k_project_bwd(
+    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
+    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
+    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
+    const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
+    float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
+    float* __restrict__ grad_opacity, float* __restrict__ grad_color) {
+  project_bwd<false>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv, g_alpha, g_ld, nullptr,
+                     grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color);
+}
+
+__global__ __launch_bounds__(kThreads) void k_project_bwd_depth(
+    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
+    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
+    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
+    const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
+    const float* __restrict__ g_depth, float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
+    float* __restrict__ grad_opacity, float* __restrict__ grad_color) {
+  project_bwd<true>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv, g_alpha, g_ld, g_depth,
+                    grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color);
+}
+
 int grid_for(i64 n) { return (int)((n + kThreads - 1) / kThreads < 65536 ? (n + kThreads - 1) / kThreads : 65536); }
 
 }  // namespace
@@ -475,19 +518,70 @@ int gcp_project_forward(const float* mean, const float* quat_xyzw, const float* 
   return GCP_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+int project_gather_call(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy,
+                        int32_t* mean_xy, int64_t* boxsize, float* vinv, float* alpha, float* l_d, float* depth, bool with_depth,
+                        int64_t* index, int32_t* row_of, const uint8_t* keep, void* stream) {
+  if (n_kept < 0) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_kept == 0) return GCP_OK;
+  if (!record || !perm || !start_xy || !end_xy || !mean_xy || !boxsize || !vinv || !alpha || !l_d || (with_depth && !depth) || !index ||
+      !row_of || (((uintptr_t)record | (uintptr_t)vinv) & 15) || (((uintptr_t)start_xy | (uintptr_t)end_xy | (uintptr_t)mean_xy) & 7))
+    return GCP_ERR_INVALID_ARGUMENT;
+  if (with_depth)
+    hipLaunchKernelGGL(k_project_gather_depth, dim3(grid_for(n_kept)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)record, perm,
+                       (i64)n_kept, start_xy, end_xy, mean_xy, (i64*)boxsize, vinv, alpha, l_d, depth, (i64*)index, row_of,
+                       (const unsigned char*)keep);
+  else
+    hipLaunchKernelGGL(k_project_gather, dim3(grid_for(n_kept)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)record, perm,
+                       (i64)n_kept, start_xy, end_xy, mean_xy, (i64*)boxsize, vinv, alpha, l_d, (i64*)index, row_of,
+                       (const unsigned char*)keep);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+int project_backward_call(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                          const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                          int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                          const float* grad_l_d, const float* grad_depth, bool with_depth, float* grad_mean, float* grad_quat,
+                          float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
+  if (n_gauss < 0 || sh_degree < 0 || sh_degree > 2 || n_basis < (sh_degree + 1) * (sh_degree + 1)) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss == 0) return GCP_OK;
+  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !row_of || !grad_mean ||
+      !grad_quat || !grad_log_scale || !grad_opacity_logit || !grad_sh_coeff)
+    return GCP_ERR_INVALID_ARGUMENT;  // the upstream arrays may be NULL when no Gaussian was kept
+  const size_t lds = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
+  if (lds > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
+  if (with_depth)
+    hipLaunchKernelGGL(k_project_bwd_depth, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
+                       opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
+                       grad_l_d, grad_depth, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  else
+    hipLaunchKernelGGL(k_project_bwd, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
+                       opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
+                       grad_l_d, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int gcp_project_gather(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy,
                        int32_t* mean_xy, int64_t* boxsize, float* vinv, float* alpha, float* l_d, int64_t* index,
                        int32_t* row_of, const uint8_t* keep, void* stream) {
-  if (n_kept < 0) return GCP_ERR_INVALID_ARGUMENT;
-  if (n_kept == 0) return GCP_OK;
-  if (!record || !perm || !start_xy || !end_xy || !mean_xy || !boxsize || !vinv || !alpha || !l_d || !index || !row_of ||
-      (((uintptr_t)record | (uintptr_t)vinv) & 15) || (((uintptr_t)start_xy | (uintptr_t)end_xy | (uintptr_t)mean_xy) & 7))
-    return GCP_ERR_INVALID_ARGUMENT;
-  hipLaunchKernelGGL(k_project_gather, dim3(grid_for(n_kept)), dim3(kThreads), 0, (hipStream_t)stream, (const float4*)record, perm,
-                     (i64)n_kept, start_xy, end_xy, mean_xy, (i64*)boxsize, vinv, alpha, l_d, (i64*)index, row_of,
-                     (const unsigned char*)keep);
-  GCP_HIP(hipGetLastError());
-  return GCP_OK;
+  return project_gather_call(record, perm, n_kept, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, nullptr, false, index, row_of,
+                             keep, stream);
+}
+
+int gcp_project_gather_depth(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy,
+                             int32_t* mean_xy, int64_t* boxsize, float* vinv, float* alpha, float* l_d, float* depth, int64_t* index,
+                             int32_t* row_of, const uint8_t* keep, void* stream) {
+  return project_gather_call(record, perm, n_kept, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, depth, true, index, row_of,
+                             keep, stream);
 }
 
 int gcp_project_backward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
@@ -495,18 +589,19 @@ int gcp_project_backward(const float* mean, const float* quat_xyzw, const float*
                          int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                          const float* grad_l_d, float* grad_mean, float* grad_quat, float* grad_log_scale,
                          float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
-  if (n_gauss < 0 || sh_degree < 0 || sh_degree > 2 || n_basis < (sh_degree + 1) * (sh_degree + 1)) return GCP_ERR_INVALID_ARGUMENT;
-  if (n_gauss == 0) return GCP_OK;
-  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !row_of || !grad_mean ||
-      !grad_quat || !grad_log_scale || !grad_opacity_logit || !grad_sh_coeff)
-    return GCP_ERR_INVALID_ARGUMENT;  // the three upstream arrays may be NULL when no Gaussian was kept
-  const size_t lds = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
-  if (lds > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
-  hipLaunchKernelGGL(k_project_bwd, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
-                     opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
-                     grad_l_d, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
-  GCP_HIP(hipGetLastError());
-  return GCP_OK;
+  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, row_of,
+                               grad_vinv, grad_alpha, grad_l_d, nullptr, false, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit,
+                               grad_sh_coeff, stream);
+}
+
+int gcp_project_backward_depth(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                               const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                               int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                               const float* grad_l_d, const float* grad_depth, float* grad_mean, float* grad_quat,
+                               float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
+  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, row_of,
+                               grad_vinv, grad_alpha, grad_l_d, grad_depth, true, grad_mean, grad_quat, grad_log_scale,
+                               grad_opacity_logit, grad_sh_coeff, stream);
 }
 
 }  // extern "C"

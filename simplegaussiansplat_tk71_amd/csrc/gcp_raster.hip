@@ -59,6 +59,7 @@ constexpr int kStageBwd = 32;       // (backward; LDS also holds the per-pixel-r
 constexpr int kCkpt = kStageBwd;    // the forward saves every pixel's transmittance every kCkpt list entries
 static_assert(kStage % kCkpt == 0 && 64 % kCkpt == 0 && kCkpt <= 32, "checkpoints fall on hit-word boundaries");
 constexpr int kGradVals = 9;        // per (tile, Gaussian) slot: go, gl0..2, S(c dx), S(c dy), S(c dx dx), S(c dx dy), S(c dy dy)
+constexpr int kGradValsDepth = 10;  // (depth variant: + S(dL/dD w), the depth gradient)
 constexpr int kRowVals = 7;         // per pixel row in LDS: go, gl0..2, S(c), S(c dx), S(c dx dx)   (dy is constant along a row)
 constexpr int kRowSlots = 8;        // LDS slots per pixel row (the transposed reduction below leaves 8 values in 8 lane classes)
 constexpr int kScanChunk = 2048;    // ints per prefix-sum block
@@ -589,19 +590,36 @@ struct BlendArgs {
   int W, H, tiles_x;
 };
 
+// The depth / alpha / background variant of the blend (gcp_blend_forward_depth / gcp_blend_backward_depth).  Per pixel,
+// with w_k = T_k o_k g_k as for the colour and T_N the transmittance behind the whole list:
+//   depth = sum_k w_k z_k (not divided by alpha),   alpha = 1 - T_N,   image += T_N bg.
+// In the backward the background and the alpha map are one more, fully absorbing layer behind the list: the recursion
+// starts at R_N = dL/dI . bg - dL/dA (0 where T_N == 0: an exact zero, or an underflow whose true derivative is
+// negligible) and c_k gains dL/dD z_k.
+struct DepthArgs {
+  const float* z;           // [N] camera-space depth of every Gaussian
+  const float* bg;          // float[3] background colour, or nullptr (black)
+  float* depth;             // forward: [(H+1)(W+1)] expected depth
+  float* alpha;             // forward: [(H+1)(W+1)] 1 - T_N
+  const float* grad_depth;  // backward: dL/d(depth map), or nullptr (zero)
+  const float* grad_alpha;  // backward: dL/d(alpha map), or nullptr (zero)
+  float* tile_bg;           // backward: [n_tiles][3] per-tile sums of dL/dI T_N, or nullptr (no background gradient)
+};
+
 template <int STAGE>
 struct Staged {
   int4 box[STAGE];     // x0, y0, x1-x0, y1-y0 (clamped to the image)
   float4 geo[STAGE];   // mx, my, opacity, box mask as bits (0-15: tile columns inside the box, 16-31: tile rows)
   float4 vin[STAGE];   // Λ' = -0.5*log2(e) * Λ, Λ = [[a,b],[c,d]]: a b c d (forward) or a, b + c, d, - (backward)
-  float4 col[STAGE];   // l0 l1 l2, 1/opacity (0 if opacity == 0)
+  float4 col[STAGE];   // l0 l1 l2, 1/opacity (0 if opacity == 0; read by no kernel) — the depth variant stages z there
   // hits[w][c]: bit j set = staged entry 64*c + j reaches into the four pixel rows of wave w.  A wave walks the set
   // bits of its own words (scalar s_ff1 / s_andn2) and never sees the entries that miss it.
   unsigned long long hits[4][(STAGE + 63) / 64];
 };
 
-template <int STAGE, bool QUAD3>
-__device__ __forceinline__ void stage_entries(const BlendArgs& a, Staged<STAGE>& s, int first, int cnt, int tile_x0, int tile_y0) {
+template <int STAGE, bool QUAD3, bool DEPTH = false>
+__device__ __forceinline__ void stage_entries(const BlendArgs& a, Staged<STAGE>& s, int first, int cnt, int tile_x0, int tile_y0,
+                                              const float* z = nullptr) {
   for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
     const i64 g = a.tile_list[first + j];
     Box b;
@@ -627,7 +645,7 @@ __device__ __forceinline__ void stage_entries(const BlendArgs& a, Staged<STAGE>&
     // association of the reference's two matmuls: its per-entry chain is latency-bound and the shorter form is 6 % slower there
     s.vin[j] = QUAD3 ? make_float4(kS * a.vinv[4 * g], kS * a.vinv[4 * g + 1] + kS * a.vinv[4 * g + 2], kS * a.vinv[4 * g + 3], 0.0f)
                      : make_float4(kS * a.vinv[4 * g], kS * a.vinv[4 * g + 1], kS * a.vinv[4 * g + 2], kS * a.vinv[4 * g + 3]);
-    s.col[j] = make_float4(a.l_d[3 * g], a.l_d[3 * g + 1], a.l_d[3 * g + 2], op != 0.0f ? 1.0f / op : 0.0f);
+    s.col[j] = make_float4(a.l_d[3 * g], a.l_d[3 * g + 1], a.l_d[3 * g + 2], DEPTH ? z[g] : (op != 0.0f ? 1.0f / op : 0.0f));
   }
 }
 
@@ -647,8 +665,9 @@ inline size_t ckpt_floats(i64 n_tile_pairs, int n_tiles) {
   return (size_t)((n_tile_pairs > 0 ? n_tile_pairs : 0) / kCkpt + 2 * (i64)n_tiles + 2) * 256u;
 }
 
-template <bool CKPT>
-__global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __restrict__ image, float* __restrict__ t_ckpt) {
+template <bool CKPT, bool DEPTH>
+__device__ __forceinline__ void blend_fwd_tile(const BlendArgs& a, float* __restrict__ image, float* __restrict__ t_ckpt,
+                                               const DepthArgs& da) {
   // The blend kernels are VALU-issue bound: let a*b+c contract into v_fma_f32 here (the library is otherwise built
   // with -ffp-contract=off).  One rounding instead of two per contraction; results stay within the 1e-5 bar.
 #pragma clang fp contract(fast)
@@ -662,11 +681,11 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __r
   const unsigned lane_bits = (1u << (lane & 15)) | (1u << (16 + w * 4 + (lane >> 4)));
   const int first = a.tile_start[tile], last = a.tile_start[tile + 1];
   float* const ck = CKPT ? t_ckpt + ckpt_slot0(first, tile) * 256 + threadIdx.x : nullptr;
-  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+  float T = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, cz = 0.0f;
   for (int base = first; base < last; base += kStage) {
     const int cnt = __builtin_amdgcn_readfirstlane(min(kStage, last - base));  // scalar loop bound
     __syncthreads();
-    stage_entries<kStage, false>(a, s, base, cnt, (tile % a.tiles_x) * kTile, (tile / a.tiles_x) * kTile);
+    stage_entries<kStage, false, DEPTH>(a, s, base, cnt, (tile % a.tiles_x) * kTile, (tile / a.tiles_x) * kTile, da.z);
     __syncthreads();
     // Only the entries whose rows reach this wave (hits[w]), in list order.  Every listed entry is used, so all
     // three of its LDS records are read together, ahead of the membership branch.  (Reading one entry ahead of the
@@ -683,6 +702,7 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __r
         if (incl != 0.0f) {                             // gs_model.py:560: dropped when exactly 0
           const float wgt = T * ge.z * g;               // gs_model.py:500
           c0 += wgt * co.x; c1 += wgt * co.y; c2 += wgt * co.z;
+          if (DEPTH) cz += wgt * co.w;                  // expected depth: one more weighted channel
         }
         T = incl;
       }
@@ -717,8 +737,26 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __r
   if (CKPT) ck[(i64)((last - first + kCkpt - 1) / kCkpt) * 256] = T;  // behind the whole list
   if (px <= a.W && py <= a.H) {
     float* o = image + ((i64)py * (a.W + 1) + px) * 3;
+    if (DEPTH && da.bg) {  // composited over the background
+      c0 += T * da.bg[0]; c1 += T * da.bg[1]; c2 += T * da.bg[2];
+    }
     o[0] = c0; o[1] = c1; o[2] = c2;
+    if (DEPTH) {
+      da.depth[(i64)py * (a.W + 1) + px] = cz;
+      da.alpha[(i64)py * (a.W + 1) + px] = 1.0f - T;
+    }
   }
+}
+
+template <bool CKPT>
+__global__ __launch_bounds__(256) void k_blend_fwd(const BlendArgs a, float* __restrict__ image, float* __restrict__ t_ckpt) {
+  blend_fwd_tile<CKPT, false>(a, image, t_ckpt, DepthArgs{});
+}
+
+template <bool CKPT>
+__global__ __launch_bounds__(256) void k_blend_fwd_depth(const BlendArgs a, const DepthArgs da, float* __restrict__ image,
+                                                         float* __restrict__ t_ckpt) {
+  blend_fwd_tile<CKPT, true>(a, image, t_ckpt, da);
 }
 
 // Backward: per (tile, entry) partial sums, written to the entry's Gaussian-major slot.
@@ -749,11 +787,28 @@ __device__ __forceinline__ float slow_factor(const Staged<STAGE>& s, int j, floa
   return ((__float_as_uint(gj.w) & lane_bits) == lane_bits) ? T * (1.0f - gj.z * g_j) : T;
 }
 
-__global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int* __restrict__ tile_off,
-                                                   const float* __restrict__ t_ckpt,
-                                                   const float* __restrict__ grad_image,
-                                                   float* __restrict__ partial /*[K][kGradVals]*/) {
+// the sums of three per-pixel values over the tile in a fixed order (a butterfly per wave, then the four waves in order),
+// written by threads 0-2: no atomics, the same bits on every run
+__device__ __forceinline__ void tile_sum3(float v0, float v1, float v2, float* out) {
+  __shared__ float s_w[4][3];
+  for (int o = 32; o > 0; o >>= 1) {
+    v0 += __shfl_xor(v0, o); v1 += __shfl_xor(v1, o); v2 += __shfl_xor(v2, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_w[threadIdx.x >> 6][0] = v0; s_w[threadIdx.x >> 6][1] = v1; s_w[threadIdx.x >> 6][2] = v2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) out[threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
+}
+
+template <bool DEPTH>
+__device__ __forceinline__ void blend_bwd_tile(const BlendArgs& a, const int* __restrict__ tile_off,
+                                               const float* __restrict__ t_ckpt,
+                                               const float* __restrict__ grad_image,
+                                               float* __restrict__ partial /*[K][kGradVals or kGradValsDepth]*/,
+                                               const DepthArgs& da) {
 #pragma clang fp contract(fast)  // as in k_blend_fwd
+  constexpr int kVals = DEPTH ? kGradValsDepth : kGradVals;
   __shared__ Staged<kStageBwd> s;
   // [entry][pixel row of the tile * kRowSlots + value]; one word of padding per entry: the fold below reads with one
   // thread per entry, and a stride of 128 words would put all of them on one LDS bank
@@ -779,6 +834,19 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
   static_assert(kStageBwd <= 32, "one 32-bit word of hits per wave");
   const int nchunks = (last - first + kStageBwd - 1) / kStageBwd;
   float R = 0.0f;  // R_k of the deepest entry handled so far (the suffix behind the end of the list is empty)
+  float gz = 0.0f;  // dL/dD of this pixel (depth variant)
+  if (DEPTH) {
+    const float T_N = ck[(i64)nchunks * 256];
+    float ga = 0.0f;
+    if (px <= a.W && py <= a.H) {
+      const i64 p = (i64)py * (a.W + 1) + px;
+      if (da.grad_depth) gz = da.grad_depth[p];
+      if (da.grad_alpha) ga = da.grad_alpha[p];
+    }
+    const float cb = da.bg ? g0 * da.bg[0] + g1 * da.bg[1] + g2 * da.bg[2] : 0.0f;
+    R = (T_N != 0.0f) ? cb - ga : 0.0f;  // the absorbing layer behind the list (DepthArgs)
+    if (da.tile_bg) tile_sum3(g0 * T_N, g1 * T_N, g2 * T_N, da.tile_bg + 3 * (i64)tile);
+  }
   for (int q = nchunks - 1; q >= 0; --q) {
     const int base = first + q * kStageBwd;
     const int cnt = __builtin_amdgcn_readfirstlane(min(kStageBwd, last - base));  // scalar loop bound
@@ -787,7 +855,7 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
     const float T_end = ck[(i64)(q + 1) * 256];
     const float T_start = (q > 0) ? ck[(i64)q * 256] : 1.0f;
     __syncthreads();
-    stage_entries<kStageBwd, true>(a, s, base, cnt, ttx * kTile, tty * kTile);
+    stage_entries<kStageBwd, true, DEPTH>(a, s, base, cnt, ttx * kTile, tty * kTile, da.z);
     __syncthreads();
     // only the entries whose rows reach this wave, deepest first (the fold below skips this wave's rows for the others,
     // so nothing needs zeroing)
@@ -838,7 +906,8 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
         const bool keep = in & (incl != 0.0f);                // dropped when the inclusive product is exactly 0 (gs_model.py:560)
         Tn = in ? Tk : Tn;
         const float tg = keep ? Tk * gv : 0.0f;
-        const float c = g0 * co.x + g1 * co.y + g2 * co.z;   // dL/dI . l
+        float c = g0 * co.x + g1 * co.y + g2 * co.z;         // dL/dI . l
+        if (DEPTH) c += gz * co.w;                            // + dL/dD z
         const float d = c - R;
         float r_o = tg * d;
         const float wgt = tg * ge.z;                            // T o g (gs_model.py:500 without l)
@@ -856,17 +925,34 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
         // two need selects (3 + 1).  15 VALU instead of 7 x 4 = 28.
         float q0, q1, q2, q3, p0, p1;
         // s_nop 1: a DPP source written by the preceding VALU instruction needs two wait states
-        asm volatile(
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %4, %4 row_mirror row_mask:0xf bank_mask:0x3\n\t"    // lanes 0-7 : go
-            "v_add_f32_dpp %1, %6, %6 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             gl1
-            "v_add_f32_dpp %2, %8, %8 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             S(c)
-            "v_add_f32_dpp %3, %10, %10 row_mirror row_mask:0xf bank_mask:0xf\n\t"  // all lanes : S(c dx dx)
-            "v_add_f32_dpp %0, %5, %5 row_mirror row_mask:0xf bank_mask:0xc\n\t"    // lanes 8-15: gl0
-            "v_add_f32_dpp %1, %7, %7 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             gl2
-            "v_add_f32_dpp %2, %9, %9 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             S(c dx)
-            : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
-            : "v"(r_o), "v"(r_l0), "v"(r_l1), "v"(r_l2), "v"(r_c), "v"(r_cx), "v"(r_xx));
+        if constexpr (DEPTH) {
+          // slot 7 carries the depth gradient: lanes 8-15 of q3 take S(dL/dD w) instead of a second copy of S(c dx dx)
+          const float r_z = gz * wgt;
+          asm volatile(
+              "s_nop 1\n\t"
+              "v_add_f32_dpp %0, %4, %4 row_mirror row_mask:0xf bank_mask:0x3\n\t"    // lanes 0-7 : go
+              "v_add_f32_dpp %1, %6, %6 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             gl1
+              "v_add_f32_dpp %2, %8, %8 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             S(c)
+              "v_add_f32_dpp %3, %10, %10 row_mirror row_mask:0xf bank_mask:0x3\n\t"  //             S(c dx dx)
+              "v_add_f32_dpp %0, %5, %5 row_mirror row_mask:0xf bank_mask:0xc\n\t"    // lanes 8-15: gl0
+              "v_add_f32_dpp %1, %7, %7 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             gl2
+              "v_add_f32_dpp %2, %9, %9 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             S(c dx)
+              "v_add_f32_dpp %3, %11, %11 row_mirror row_mask:0xf bank_mask:0xc\n\t"  //             S(dL/dD w)
+              : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
+              : "v"(r_o), "v"(r_l0), "v"(r_l1), "v"(r_l2), "v"(r_c), "v"(r_cx), "v"(r_xx), "v"(r_z));
+        } else {
+          asm volatile(
+              "s_nop 1\n\t"
+              "v_add_f32_dpp %0, %4, %4 row_mirror row_mask:0xf bank_mask:0x3\n\t"    // lanes 0-7 : go
+              "v_add_f32_dpp %1, %6, %6 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             gl1
+              "v_add_f32_dpp %2, %8, %8 row_mirror row_mask:0xf bank_mask:0x3\n\t"    //             S(c)
+              "v_add_f32_dpp %3, %10, %10 row_mirror row_mask:0xf bank_mask:0xf\n\t"  // all lanes : S(c dx dx)
+              "v_add_f32_dpp %0, %5, %5 row_mirror row_mask:0xf bank_mask:0xc\n\t"    // lanes 8-15: gl0
+              "v_add_f32_dpp %1, %7, %7 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             gl2
+              "v_add_f32_dpp %2, %9, %9 row_mirror row_mask:0xf bank_mask:0xc\n\t"    //             S(c dx)
+              : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)
+              : "v"(r_o), "v"(r_l0), "v"(r_l1), "v"(r_l2), "v"(r_c), "v"(r_cx), "v"(r_xx));
+        }
         asm volatile(
             "s_nop 1\n\t"
             "v_add_f32_dpp %0, %2, %2 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"  // bit 2 clear: from q0 / q2
@@ -899,9 +985,9 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
       const int4 bx = s.box[j];
       const int ntx = ((bx.x + bx.z) >> 4) - (bx.x >> 4) + 1;
       const i64 e = (i64)tile_off[g] + (i64)(tty - (bx.y >> 4)) * ntx + (ttx - (bx.x >> 4));
-      float* out = partial + e * kGradVals;
+      float* out = partial + e * kVals;
       const float my = s.geo[j].y;
-      float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f, cx = 0.0f, cy = 0.0f, xx = 0.0f, xy = 0.0f, yy = 0.0f;
+      float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f, cx = 0.0f, cy = 0.0f, xx = 0.0f, xy = 0.0f, yy = 0.0f, zz = 0.0f;
 #pragma unroll
       for (int wv = 0; wv < 4; ++wv) {
         if (!((s.hits[wv][0] >> j) & 1ull)) continue;  // that wave never wrote its rows for this entry
@@ -912,11 +998,26 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
           o0 += d[0]; o1 += d[1]; o2 += d[2]; o3 += d[3];
           cx += d[5]; cy += dy * d[4];
           xx += d[6]; xy += dy * d[5]; yy += dy * dy * d[4];
+          if (DEPTH) zz += d[7];
         }
       }
       out[0] = o0; out[1] = o1; out[2] = o2; out[3] = o3; out[4] = cx; out[5] = cy; out[6] = xx; out[7] = xy; out[8] = yy;
+      if (DEPTH) out[9] = zz;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int* __restrict__ tile_off,
+                                                   const float* __restrict__ t_ckpt,
+                                                   const float* __restrict__ grad_image,
+                                                   float* __restrict__ partial /*[K][kGradVals]*/) {
+  blend_bwd_tile<false>(a, tile_off, t_ckpt, grad_image, partial, DepthArgs{});
+}
+
+__global__ __launch_bounds__(256) void k_blend_bwd_depth(const BlendArgs a, const DepthArgs da, const int* __restrict__ tile_off,
+                                                         const float* __restrict__ t_ckpt, const float* __restrict__ grad_image,
+                                                         float* __restrict__ partial /*[K][kGradValsDepth]*/) {
+  blend_bwd_tile<true>(a, tile_off, t_ckpt, grad_image, partial, da);
 }
 
 // per Gaussian: sum its tile slots in order, expand the moments into the four gradients.
@@ -925,14 +1026,16 @@ __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int*
 // wave: lane l takes slots e0 + l, e0 + l + 64, ... in order, and the 64 partial sums are added in a fixed butterfly.  Which
 // Gaussians go that way depends on their slot count alone, so the result is the same from run to run.
 constexpr int kReduceWide = 128;  // tile slots from which a Gaussian is summed by the wave
-__global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ partial, const int* __restrict__ tile_off,
-                                                     const int* __restrict__ tile_start, int n_tiles, const float* __restrict__ vinv, i64 n,
-                                                     i64 capacity, float* grad_mean, float* grad_vinv, float* grad_opacity, float* grad_l) {
+template <int NV>
+__device__ __forceinline__ void grad_reduce(const float* __restrict__ partial, const int* __restrict__ tile_off,
+                                            const int* __restrict__ tile_start, int n_tiles, const float* __restrict__ vinv, i64 n,
+                                            i64 capacity, float* grad_mean, float* grad_vinv, float* grad_opacity, float* grad_l,
+                                            float* grad_z) {
   const i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  float r[kGradVals];
+  float r[NV];
 #pragma unroll
-  for (int v = 0; v < kGradVals; ++v) r[v] = 0.0f;
+  for (int v = 0; v < NV; ++v) r[v] = 0.0f;
   // Only slots the blend kernel wrote are summed: a Gaussian's entries [tile_off[g], tile_off[g+1]) count iff they lie
   // inside what the binning LISTED (tile_start[n_tiles] entries: everything with exact binning; with a capture-safe
   // capacity the Gaussians that fit; nothing at all when the int32 prefix sums wrapped at > 2^31 entries — the offsets
@@ -949,19 +1052,19 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ p
   if (!wide) {
     for (i64 e = e0; e < e1; ++e)
 #pragma unroll
-      for (int v = 0; v < kGradVals; ++v) r[v] += partial[e * kGradVals + v];
+      for (int v = 0; v < NV; ++v) r[v] += partial[e * NV + v];
   }
   for (unsigned long long todo = __ballot(wide); todo; todo &= todo - 1ull) {  // wave-uniform: one wide Gaussian at a time
     const int owner = __builtin_ctzll(todo);
     const i64 f0 = (i64)__builtin_amdgcn_readlane((int)e0, owner), f1 = (i64)__builtin_amdgcn_readlane((int)e1, owner);  // (entries < 2^31)
-    float p[kGradVals];
+    float p[NV];
 #pragma unroll
-    for (int v = 0; v < kGradVals; ++v) p[v] = 0.0f;
+    for (int v = 0; v < NV; ++v) p[v] = 0.0f;
     for (i64 e = f0 + lane; e < f1; e += 64)
 #pragma unroll
-      for (int v = 0; v < kGradVals; ++v) p[v] += partial[e * kGradVals + v];
+      for (int v = 0; v < NV; ++v) p[v] += partial[e * NV + v];
 #pragma unroll
-    for (int v = 0; v < kGradVals; ++v) {
+    for (int v = 0; v < NV; ++v) {
       float t = p[v];
       for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);  // a fixed butterfly: every lane ends with the same sum
       if (lane == owner) r[v] = t;
@@ -979,6 +1082,39 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ p
   grad_vinv[4 * g + 1] = -0.5f * r[7];
   grad_vinv[4 * g + 2] = -0.5f * r[7];
   grad_vinv[4 * g + 3] = -0.5f * r[8];
+  if (NV > kGradVals) grad_z[g] = r[NV - 1];
+}
+
+__global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ partial, const int* __restrict__ tile_off,
+                                                     const int* __restrict__ tile_start, int n_tiles, const float* __restrict__ vinv, i64 n,
+                                                     i64 capacity, float* grad_mean, float* grad_vinv, float* grad_opacity, float* grad_l) {
+  grad_reduce<kGradVals>(partial, tile_off, tile_start, n_tiles, vinv, n, capacity, grad_mean, grad_vinv, grad_opacity, grad_l, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_grad_reduce_depth(const float* __restrict__ partial, const int* __restrict__ tile_off,
+                                                           const int* __restrict__ tile_start, int n_tiles, const float* __restrict__ vinv,
+                                                           i64 n, i64 capacity, float* grad_mean, float* grad_vinv, float* grad_opacity,
+                                                           float* grad_l, float* grad_z) {
+  grad_reduce<kGradValsDepth>(partial, tile_off, tile_start, n_tiles, vinv, n, capacity, grad_mean, grad_vinv, grad_opacity, grad_l,
+                              grad_z);
+}
+
+// dL/dbg: the per-tile sums k_blend_bwd_depth wrote, added by ONE block in a fixed order (a strided sum per thread, then a
+// tree) — the same bits on every run
+__global__ __launch_bounds__(256) void k_bg_reduce(const float* __restrict__ tile_bg, int n_tiles, float* __restrict__ grad_bg) {
+  __shared__ float s[3][256];
+  float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+  for (int t = threadIdx.x; t < n_tiles; t += 256) {
+    a0 += tile_bg[3 * (i64)t]; a1 += tile_bg[3 * (i64)t + 1]; a2 += tile_bg[3 * (i64)t + 2];
+  }
+  s[0][threadIdx.x] = a0; s[1][threadIdx.x] = a1; s[2][threadIdx.x] = a2;
+  for (int o = 128; o > 0; o >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < o)
+      for (int c = 0; c < 3; ++c) s[c][threadIdx.x] += s[c][threadIdx.x + o];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) grad_bg[threadIdx.x] = s[threadIdx.x][0];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1742,6 +1878,73 @@ int gcp_blend_backward(const int32_t* start_xy, const int32_t* end_xy, const flo
                      (const float*)partial, tile_off, tile_start, tg.tx * tg.ty, vinv, (i64)n_gauss, (i64)n_tile_pairs, grad_mean,
                      grad_vinv, grad_opacity, grad_l);
   GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+int gcp_blend_forward_depth(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                            const float* opacity, const float* l_d, const float* depth, const float* background, int64_t n_gauss,
+                            int32_t width, int32_t height, const int32_t* tile_start, const int32_t* tile_list, float* image,
+                            float* depth_map, float* alpha_map, float* t_ckpt, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  BlendArgs a;
+  const int st = make_args(a, start_xy, end_xy, mean_xy, vinv, opacity, l_d, width, height, tile_start, tile_list);
+  if (st != GCP_OK || !image || !depth_map || !alpha_map || n_gauss < 0) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss > 0 && (!start_xy || !end_xy || !mean_xy || !vinv || !opacity || !l_d || !depth || !tile_list))
+    return GCP_ERR_INVALID_ARGUMENT;
+  DepthArgs da{};
+  da.z = depth; da.bg = background; da.depth = depth_map; da.alpha = alpha_map;
+  const TileGrid tg = tile_grid(width, height);
+  if (t_ckpt) hipLaunchKernelGGL((k_blend_fwd_depth<true>), dim3((unsigned)(tg.tx * tg.ty)), dim3(256), 0, stream, a, da, image, t_ckpt);
+  else hipLaunchKernelGGL((k_blend_fwd_depth<false>), dim3((unsigned)(tg.tx * tg.ty)), dim3(256), 0, stream, a, da, image, (float*)nullptr);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+size_t gcp_blend_backward_depth_workspace_bytes(int64_t n_tile_pairs, int32_t width, int32_t height) {
+  if (width < 0 || height < 0) return 0;
+  const TileGrid tg = tile_grid(width, height);
+  // per-entry partial sums, then the per-tile background sums
+  return align256((size_t)(n_tile_pairs > 0 ? n_tile_pairs : 1) * kGradValsDepth * sizeof(float)) +
+         align256((size_t)tg.tx * tg.ty * 3 * sizeof(float));
+}
+
+int gcp_blend_backward_depth(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                             const float* opacity, const float* l_d, const float* depth, const float* background, int64_t n_gauss,
+                             int32_t width, int32_t height, const int32_t* tile_off, int64_t n_tile_pairs,
+                             const int32_t* tile_start, const int32_t* tile_list, const float* t_ckpt, const float* grad_image,
+                             const float* grad_depth_map, const float* grad_alpha_map, float* grad_mean, float* grad_vinv,
+                             float* grad_opacity, float* grad_l, float* grad_depth, float* grad_background, void* ws,
+                             size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  BlendArgs a;
+  const int st = make_args(a, start_xy, end_xy, mean_xy, vinv, opacity, l_d, width, height, tile_start, tile_list);
+  if (st != GCP_OK || n_gauss < 0 || n_tile_pairs < 0 || !t_ckpt || !grad_image) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss > 0 && (!start_xy || !end_xy || !mean_xy || !vinv || !opacity || !l_d || !depth || !tile_off || !tile_list ||
+                      !grad_mean || !grad_vinv || !grad_opacity || !grad_l || !grad_depth))
+    return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss == 0 && !grad_background) return GCP_OK;
+  if (!ws) return GCP_ERR_INVALID_ARGUMENT;
+  if (ws_bytes < gcp_blend_backward_depth_workspace_bytes(n_tile_pairs, width, height)) return GCP_ERR_WORKSPACE;
+  const TileGrid tg = tile_grid(width, height);
+  const int n_tiles = tg.tx * tg.ty;
+  float* partial = (float*)ws;
+  float* tile_bg = (float*)((char*)ws + align256((size_t)(n_tile_pairs > 0 ? n_tile_pairs : 1) * kGradValsDepth * sizeof(float)));
+  DepthArgs da{};
+  da.z = depth; da.bg = background; da.grad_depth = grad_depth_map; da.grad_alpha = grad_alpha_map;
+  da.tile_bg = grad_background ? tile_bg : nullptr;
+  // every tile, also one without entries: the background gradient needs every pixel's T_N
+  hipLaunchKernelGGL(k_blend_bwd_depth, dim3((unsigned)n_tiles), dim3(256), 0, stream, a, da, tile_off, t_ckpt, grad_image, partial);
+  GCP_HIP(hipGetLastError());
+  if (n_gauss > 0) {
+    hipLaunchKernelGGL(k_grad_reduce_depth, dim3((unsigned)((n_gauss + 255) / 256)), dim3(256), 0, stream,
+                       (const float*)partial, tile_off, tile_start, n_tiles, vinv, (i64)n_gauss, (i64)n_tile_pairs, grad_mean,
+                       grad_vinv, grad_opacity, grad_l, grad_depth);
+    GCP_HIP(hipGetLastError());
+  }
+  if (grad_background) {
+    hipLaunchKernelGGL(k_bg_reduce, dim3(1), dim3(256), 0, stream, (const float*)tile_bg, n_tiles, grad_background);
+    GCP_HIP(hipGetLastError());
+  }
   return GCP_OK;
 }
 

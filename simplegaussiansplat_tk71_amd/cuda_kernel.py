@@ -63,6 +63,8 @@ __all__ = [
     "create_alpha_brend_boxes",
     "grad_cumsum_boxes",
     "custom_autograd_grouped_cumprod",
+    "RenderDepth",
+    "render",
     "tile_capacity",
     "capacity_exceeded",
     "GraphedStep",
@@ -625,3 +627,57 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
             )
         g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
         return None, None, None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, None, None
+
+
+class RenderDepth(torch.autograd.Function):
+    """The Function's blend with an expected-depth map, an alpha map and a background colour (csrc/gcp_raster.hip,
+    k_blend_fwd_depth / k_blend_bwd_depth); see `render`.  Capture-safe and overflow-reporting under `tile_capacity` /
+    `GraphedStep` as `custom_autograd_grouped_cumprod`."""
+
+    @staticmethod
+    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background):
+        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
+        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
+        with torch.no_grad():
+            w, h = int(image_width), int(image_height)
+            bins = _raster.bin_tiles(startpoint, endpoint, w, h, capacity=_capacity)
+            if bins.info is not None:  # sticky, as in custom_autograd_grouped_cumprod
+                flag = _sticky_flag(bins.info.device)
+                torch.maximum(flag, bins.info[1:2], out=flag)
+            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                     l_d, depth, background, with_checkpoints=True)
+        ctx.bins_meta = (bins.width, bins.height, bins.n_gauss, bins.n_tile_pairs, bins.tiles_x, bins.tiles_y)
+        ctx.save_for_backward(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, bins.tile_off,
+                              bins.tile_start, bins.tile_list)
+        return image, dmap, alpha
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_alpha):
+        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, tile_off, tile_start,
+         tile_list) = ctx.saved_tensors
+        bins = _raster.TileBins(*ctx.bins_meta, tile_off, tile_start, tile_list)
+        want_bg = background is not None and ctx.needs_input_grad[9]
+        with torch.no_grad():
+            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
+                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
+                background, background_grad=want_bg)
+        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
+        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
+                g_bg.reshape(background.shape) if want_bg else None)
+
+
+def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None):
+    """Rasterise and blend one camera's depth-ordered Gaussians (the arguments of `custom_autograd_grouped_cumprod`, without
+    boxsize / batch) -> (image (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), differentiable in mean (if float),
+    variance_inverse, opacity, l_d, depth and background.
+
+    Per pixel p, with w_k = T_k o_k g_k the colour weights (a pair whose inclusive product is exactly 0 is dropped: w_k = 0,
+    zero gradient) and T_N the transmittance behind p's whole list:
+      alpha(p) = 1 - T_N(p)
+      depth(p) = sum_k w_k z_k, `depth` [N] being the Gaussians' camera-space depths — NOT divided by alpha: a caller who
+                 wants the normalised depth divides by alpha;
+      image(p) = sum_k w_k l_k + T_N(p) * background.
+    `background`: a float[3] tensor on the device (no host read: a captured step may change it between replays), or None
+    for black — the image is then `custom_autograd_grouped_cumprod`'s bit for bit.  The gradient of the background is summed
+    over the pixels in a fixed order (the same bits on every run)."""
+    return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)

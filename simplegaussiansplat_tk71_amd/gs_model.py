@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from . import raster as _raster
-from .cuda_kernel import custom_autograd_grouped_cumprod
+from .cuda_kernel import custom_autograd_grouped_cumprod, render
 
 __all__ = [
     "GS_dataset",
@@ -93,11 +93,12 @@ def _box_clamp(width, height, tile_max_width):
 
 class _ProjectCamera(torch.autograd.Function):
     """One camera of `camera_inputs` on the HIP library (csrc/gcp_project.hip): gcp_project_forward, the library's
-    stable radix sort on the depth keys, gcp_project_gather; backward = gcp_project_backward."""
+    stable radix sort on the depth keys, gcp_project_gather; backward = gcp_project_backward.  with_depth: the camera-space
+    depths too, right after l_d (gcp_project_gather_depth / gcp_project_backward_depth)."""
 
     @staticmethod
     def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
-                capture_safe=False):
+                capture_safe=False, with_depth=False):
         dev, n = mean.device, mean.shape[0]
         args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
         for t in args:
@@ -123,32 +124,40 @@ class _ProjectCamera(torch.autograd.Function):
             perm = _raster.stable_sort_keys(sort_key, key_bits=31)[1] if n else sort_key
             start, end, mean_xy, boxsize = i32(m, 2), i32(m, 2), i32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
             vinv, alpha, l_d, index = f32(m, 2, 2), f32(m, 1), f32(m, 3), torch.empty(m, dtype=torch.int64, device=dev)
-            _lib.check(lib.gcp_project_gather(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
-                                              mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
-                                              l_d.data_ptr(), index.data_ptr(), row_of.data_ptr(),
-                                              keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather")
+            if with_depth:
+                depth = f32(m)
+                _lib.check(lib.gcp_project_gather_depth(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
+                                                        mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
+                                                        l_d.data_ptr(), depth.data_ptr(), index.data_ptr(), row_of.data_ptr(),
+                                                        keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather_depth")
+            else:
+                _lib.check(lib.gcp_project_gather(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
+                                                  mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
+                                                  l_d.data_ptr(), index.data_ptr(), row_of.data_ptr(),
+                                                  keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather")
         keep = keep.view(torch.bool)
         ctx.save_for_backward(*args, row_of)
-        ctx.L_max = L_max
-        out = (vinv, alpha, l_d, start, end, mean_xy, boxsize, index, keep)
-        ctx.mark_non_differentiable(*out[3:])
+        ctx.L_max, ctx.with_depth = L_max, with_depth
+        out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), start, end, mean_xy, boxsize, index, keep)
+        ctx.mark_non_differentiable(*out[-6:])
         return out
 
     @staticmethod
-    def backward(ctx, g_vinv, g_alpha, g_ld, *_):
+    def backward(ctx, g_vinv, g_alpha, g_ld, *rest):
         *args, row_of = ctx.saved_tensors
         mean, variance_q, variance_scale, opacity, color = args[:5]
         grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
-        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld)]
+        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:1 if ctx.with_depth else 0])]
         with torch.cuda.device(mean.device):
             stream = torch.cuda.current_stream(mean.device).cuda_stream
-            _lib.check(_lib.load().gcp_project_backward(
-                *(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1], row_of.data_ptr(),
-                *(t.data_ptr() for t in g), *(t.data_ptr() for t in grads), stream), "gcp_project_backward")
-        return (*grads, None, None, None, None, None, None, None)
+            entry = _lib.load().gcp_project_backward_depth if ctx.with_depth else _lib.load().gcp_project_backward
+            _lib.check(entry(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1], row_of.data_ptr(),
+                             *(t.data_ptr() for t in g), *(t.data_ptr() for t in grads), stream), "gcp_project_backward")
+        return (*grads, None, None, None, None, None, None, None, None)
 
 
-def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False):
+def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
+                  with_depth=False):
     """Per camera, the depth-ordered, culled arguments of the Function (reference: gs_model.py:277-425).
 
     mean (N,3), variance_q (N,4 xyzw), variance_scale (N,3 log), opacity (N,1 logit), color (N,(L+1)^2,3),
@@ -163,18 +172,27 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
     capture_safe=True: no device->host read at all (pass `wh` as a CPU tensor or a list): every camera's list keeps all N
     Gaussians in depth order, the culled ones behind the kept ones with EMPTY boxes (binned into no tile, zero
     gradients), and no camera is ever dropped; images and gradients are those of the default mode.  Together with
-    `cuda_kernel.tile_capacity` the projection + Function forward and backward queue without waiting for the GPU."""
+    `cuda_kernel.tile_capacity` the projection + Function forward and backward queue without waiting for the GPU.
+
+    with_depth=True: every dict also holds "depth", the Gaussians' camera-space depths in list order (the positive depth
+    they are sorted by; 0 for the culled entries of a capture-safe list), differentiable w.r.t. `mean` — the `depth`
+    argument of `cuda_kernel.render`."""
     width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
     clamp = _box_clamp(width, height, tile_max_width)
     grad_iter = None
     cams = []
     for c in range(P.shape[0]):
-        vinv, alpha, l_d, start, end, mean_xy, boxsize, index, keep = _ProjectCamera.apply(
-            mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max, capture_safe)
+        out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
+                                   capture_safe, with_depth)
+        vinv, alpha, l_d = out[:3]
+        start, end, mean_xy, boxsize, index, keep = out[-6:]
         grad_iter = keep if grad_iter is None else grad_iter | keep
-        cams.append(None if index.numel() == 0 else {
+        cam = None if index.numel() == 0 else {
             "boxsize": boxsize, "startpoint": start, "endpoint": end, "mean": mean_xy, "variance_inverse": vinv,
-            "opacity": alpha, "l_d": l_d, "index": index})
+            "opacity": alpha, "l_d": l_d, "index": index}
+        if cam is not None and with_depth:
+            cam["depth"] = out[3]
+        cams.append(cam)
     if grad_iter is None:
         grad_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.bool)
     return cams, grad_iter, (width, height)
@@ -380,9 +398,9 @@ class GS_model_with_param(torch.nn.Module):
         self.changing_optimizer()
 
     # ---- forward (:277-460) ------------------------------------------------------------------------------------
-    def camera_inputs(self, P, K, wh):
+    def camera_inputs(self, P, K, wh, with_depth=False):
         return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
-                             self.variance_pixel_tile_max_width, self._L_max)
+                             self.variance_pixel_tile_max_width, self._L_max, with_depth=with_depth)
 
     def forward(self, P, K, wh, image_sample):
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh)
@@ -401,6 +419,32 @@ class GS_model_with_param(torch.nn.Module):
         h, w = int(height), int(width)
         out = out.reshape(-1, 3, h, w) if self.reference_layout else out.permute(0, 3, 1, 2).contiguous()
         return [out, names, grad_iter]
+
+    def render(self, P, K, wh, background=None, image_sample=None):
+        """`forward` with the expected-depth and alpha maps and a background colour (`cuda_kernel.render`, whose
+        docstring pins the definitions: depth = sum of the colour weights times the camera-space depth, NOT divided by
+        alpha; alpha = 1 - the transmittance behind the pixel; image composited over `background`, a float[3] device tensor
+        or None for black).  Returns [images (B, 3, H, W), depth (B, 1, H, W), alpha (B, 1, H, W), names, grad_iter], all
+        maps after the same [1:, 1:] crop as `forward`; `names` are `image_sample`'s entries (default: camera indices) of the
+        cameras that see anything — the others are dropped, as in `forward`."""
+        cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
+        names_in = list(range(P.shape[0])) if image_sample is None else image_sample
+        images, depths, alphas, names = [], [], [], []
+        for cam, name in zip(cams, names_in):
+            if cam is None:
+                continue
+            img, dep, alp = render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
+                                   cam["l_d"], cam["depth"], width, height, background)
+            images.append(img)
+            depths.append(dep)
+            alphas.append(alp)
+            names.append(name)
+        if not images:
+            raise RuntimeError("no camera of the batch sees any Gaussian")
+        images = torch.stack(images)[:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
+        depth = torch.stack(depths)[:, None, 1:, 1:].contiguous()
+        alpha = torch.stack(alphas)[:, None, 1:, 1:].contiguous()
+        return [images, depth, alpha, names, grad_iter]
 
 
 _WINDOW_CACHE = {}

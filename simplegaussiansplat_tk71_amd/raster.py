@@ -220,6 +220,97 @@ def blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity, 
     return g_mean, g_vinv, g_op, g_l
 
 
+def _depth_args(depth, background, n, dev):
+    z = _dev_tensor(depth, "depth", torch.float32).reshape(-1)
+    _require(z.numel() == n, f"depth: {z.numel()} values, expected {n}")
+    _require(z.device == dev, f"depth: on {z.device}, expected {dev}")
+    bg = None
+    if background is not None:
+        bg = _dev_tensor(background, "background", torch.float32).reshape(-1)
+        _require(bg.numel() == 3, "background: expected 3 floats (an RGB colour) on the device")
+        _require(bg.device == dev, f"background: on {bg.device}, expected {dev}")
+    return z, bg
+
+
+def blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background=None,
+                        with_checkpoints=False):
+    """`blend_forward` that also returns the expected-depth and alpha maps and composites a background colour
+    (gcp_blend_forward_depth).  Per pixel, w_k = T_k o_k g_k being the colour weights and T_N the transmittance behind the
+    whole list: depth_map = sum_k w_k z_k — NOT divided by alpha: divide for the normalised depth —, alpha = 1 - T_N,
+    image = sum_k w_k l_k + T_N * background.  `depth`: [N] per Gaussian; `background`: float[3] on the device (no host
+    read; may change between replays of a captured graph) or None = black, the image then bit for bit `blend_forward`'s.
+    -> (image f32[H+1, W+1, 3], depth_map f32[H+1, W+1], alpha f32[H+1, W+1]) [+ t_ckpt]."""
+    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
+    dev = start.device
+    z, bg = _depth_args(depth, background, start.size(0), dev)
+    lib = _lib.load()
+    image = torch.empty(bins.height + 1, bins.width + 1, 3, dtype=torch.float32, device=dev)
+    dmap = torch.empty(bins.height + 1, bins.width + 1, dtype=torch.float32, device=dev)
+    alpha = torch.empty(bins.height + 1, bins.width + 1, dtype=torch.float32, device=dev)
+    ckpt = None
+    if with_checkpoints:
+        ckpt = torch.empty(lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height), dtype=torch.float32,
+                           device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(
+            lib.gcp_blend_forward_depth(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
+                                        col.data_ptr(), z.data_ptr(), bg.data_ptr() if bg is not None else None, bins.n_gauss,
+                                        bins.width, bins.height, bins.tile_start.data_ptr(), bins.tile_list.data_ptr(),
+                                        image.data_ptr(), dmap.data_ptr(), alpha.data_ptr(),
+                                        ckpt.data_ptr() if with_checkpoints else None, _stream(dev)),
+            "gcp_blend_forward_depth",
+        )
+    return (image, dmap, alpha, ckpt) if with_checkpoints else (image, dmap, alpha)
+
+
+def blend_backward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, grad_image,
+                         grad_depth=None, grad_alpha=None, background=None, background_grad=False):
+    """Backward of `blend_forward_depth` (gcp_blend_backward_depth) for the loss <image, grad_image> + <depth_map,
+    grad_depth> + <alpha, grad_alpha> (None: zero) -> (grad_mean [N,2], grad_variance_inverse [N,2,2], grad_opacity [N,1],
+    grad_l_d [N,3], grad_depth [N], grad_background [3] or None).  Dropped pairs get zero gradients; where T_N is 0 the
+    background and alpha terms have none.  `background_grad`: also return dL/dbackground = sum_p grad_image(p) T_N(p)
+    (summed in a fixed order).  `grad_image` None: zero."""
+    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
+    dev = start.device
+    n = bins.n_gauss
+    z, bg = _depth_args(depth, background, start.size(0), dev)
+    shape = (bins.height + 1, bins.width + 1)
+    if grad_image is None:
+        grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
+    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
+    _require(tuple(gimg.shape) == shape + (3,), f"grad_image: expected shape {shape + (3,)}")
+    maps = []
+    for t, name in ((grad_depth, "grad_depth"), (grad_alpha, "grad_alpha")):
+        if t is not None:
+            t = _dev_tensor(t, name, torch.float32)
+            _require(tuple(t.shape) == shape, f"{name}: expected shape {shape}")
+        maps.append(t)
+    lib = _lib.load()
+    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
+    _require(ck.numel() >= lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height),
+             "t_ckpt: too small for these bins (pass what blend_forward_depth(..., with_checkpoints=True) returned)")
+    g_mean = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    g_vinv = torch.empty(n, 2, 2, dtype=torch.float32, device=dev)
+    g_op = torch.empty(n, 1, dtype=torch.float32, device=dev)
+    g_l = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    g_z = torch.empty(n, dtype=torch.float32, device=dev)
+    g_bg = torch.empty(3, dtype=torch.float32, device=dev) if background_grad else None
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_blend_backward_depth_workspace_bytes(bins.tile_capacity, bins.width, bins.height), dtype=torch.uint8,
+                         device=dev)
+        _lib.check(
+            lib.gcp_blend_backward_depth(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
+                                         col.data_ptr(), z.data_ptr(), bg.data_ptr() if bg is not None else None, n, bins.width,
+                                         bins.height, bins.tile_off.data_ptr(), bins.tile_capacity, bins.tile_start.data_ptr(),
+                                         bins.tile_list.data_ptr(), ck.data_ptr(), gimg.data_ptr(),
+                                         *(t.data_ptr() if t is not None else None for t in maps),
+                                         g_mean.data_ptr(), g_vinv.data_ptr(), g_op.data_ptr(), g_l.data_ptr(), g_z.data_ptr(),
+                                         g_bg.data_ptr() if g_bg is not None else None, ws.data_ptr(), ws.numel(), _stream(dev)),
+            "gcp_blend_backward_depth",
+        )
+    return g_mean, g_vinv, g_op, g_l, g_z, g_bg
+
+
 def exclusive_scan_i32(x):
     """int32[n] -> int32[n+1] exclusive prefix sums (last entry = total)."""
     x = _dev_tensor(x, "x", torch.int32)

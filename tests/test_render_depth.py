@@ -1,0 +1,69 @@
+"""Depth / alpha / background blend (gcp_blend_*_depth, gcp_project_*_depth) without a GPU: the argument checks of the new
+entry points return before any HIP call, and the new kernel instantiations hold their registers without scratch."""
+import re
+import subprocess
+
+import pytest
+import torch
+
+
+def test_depth_entry_points_validate_without_a_gpu():
+    from simplegaussiansplat_tk71_amd import _lib
+
+    lib = _lib.load()
+    n = None
+    # forward: image, depth and alpha maps are required; negative sizes and missing inputs are refused
+    assert lib.gcp_blend_forward_depth(*[n] * 8, 5, 10, 10, *[n] * 7) == 1
+    assert lib.gcp_blend_forward_depth(*[n] * 8, -1, 10, 10, *[n] * 7) == 1
+    assert lib.gcp_blend_forward_depth(*[n] * 8, 5, -1, 10, *[n] * 7) == 1
+    # backward: t_ckpt and grad_image are required, and every per-Gaussian array when there are Gaussians
+    assert lib.gcp_blend_backward_depth(*[n] * 8, 5, 10, 10, n, 0, *[n] * 13, 0, n) == 1
+    assert lib.gcp_blend_backward_depth(*[n] * 8, -1, 10, 10, n, 0, *[n] * 13, 0, n) == 1
+    assert lib.gcp_blend_backward_depth(*[n] * 8, 0, 10, 10, n, -1, *[n] * 13, 0, n) == 1
+    # workspace: 10 floats per (tile, Gaussian) entry, then 3 per tile, each part 256-byte aligned
+    assert lib.gcp_blend_backward_depth_workspace_bytes(3_000_000, 1919, 1079) == 3_000_000 * 10 * 4 + (120 * 68 * 3 * 4 + 255) // 256 * 256
+    assert lib.gcp_blend_backward_depth_workspace_bytes(0, 15, 15) == 256 + 256
+    assert lib.gcp_blend_backward_depth_workspace_bytes(5, -1, 15) == 0
+    # projection: the depth output is required
+    assert lib.gcp_project_gather_depth(n, n, 4, *[n] * 12) == 1
+    assert lib.gcp_project_gather_depth(n, n, -1, *[n] * 12) == 1
+    assert lib.gcp_project_gather_depth(n, n, 0, *[n] * 12) == 0  # nothing kept: a no-op
+    assert lib.gcp_project_backward_depth(*[n] * 7, 4, 2, 9, *[n] * 11) == 1
+    assert lib.gcp_project_backward_depth(*[n] * 7, 4, 3, 16, *[n] * 11) == 1
+
+
+def test_render_rejects_cpu_tensors():
+    import cuda_kernel as ck
+
+    z = torch.zeros(3, 2, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        ck.render(z, z, z, torch.zeros(3, 2, 2), torch.ones(3, 1), torch.ones(3, 3), torch.ones(3), 16, 16)
+    assert "render" in ck.__all__ and "RenderDepth" in ck.__all__
+
+
+def test_depth_blend_kernels_use_no_scratch_and_keep_six_waves(tmp_path):
+    """The depth variants of the blend (k_blend_fwd_depth, k_blend_bwd_depth) and their reduces are built from the same
+    bodies as the colour-only kernels: no scratch, no spills, <= 80 VGPRs (six waves per SIMD) for the blend kernels."""
+    from simplegaussiansplat_tk71_amd import _build
+
+    found = {}
+    for name in ("gcp_raster.hip", "gcp_project.hip"):
+        src = [s for s in _build.SRCS if s.endswith(name)][0]
+        out = tmp_path / (name + ".s")
+        flags = [f for f in _build.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
+        res = subprocess.run([_build.find_hipcc(), *flags, "-I", _build.INCLUDE, "-S", "--cuda-device-only", "-o", str(out), src],
+                             capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr[-2000:]
+        kernels = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
+                             r"(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", out.read_text())
+        for k, scratch, vgpr, spills in kernels:
+            found[k] = (int(scratch), int(vgpr), int(spills))
+    new = {frag: [k for k in found if frag in k] for frag in ("k_blend_fwd_depth", "k_blend_bwd_depth", "k_grad_reduce_depth", "k_bg_reduce",
+                                                              "k_project_gather_depth", "k_project_bwd_depth")}
+    assert len(new["k_blend_fwd_depth"]) == 2 and all(len(v) == 1 for f, v in new.items() if f != "k_blend_fwd_depth"), new
+    for frag, ks in new.items():
+        for k in ks:
+            scratch, vgpr, spills = found[k]
+            assert scratch == 0 and spills == 0, (k, scratch, spills)
+            if "k_blend" in frag:
+                assert vgpr <= 80, (k, vgpr)
