@@ -19,6 +19,6 @@ setup(
     description="MI355X-native grouped cumprod/cumsum (alpha-compositing scan) drop-in",
     packages=["simplegaussiansplat_tk71_amd"],
     py_modules=["grouped_cumprod", "cuda_kernel"],
-    package_data={"simplegaussiansplat_tk71_amd": ["lib/*.so", "csrc/*.hip"]},
+    package_data={"simplegaussiansplat_tk71_amd": ["lib/*.so", "csrc/*.hip", "csrc/*.hpp"]},
     cmdclass={"build_ext": build_ext},
 )

@@ -44,7 +44,7 @@ SIGNATURES = {
     "gcp_last_fallback_tiles": (ctypes.c_int, [_c_void_p, _c_void_p, ctypes.POINTER(_i64)]),
     "gcp_last_lookback_tiles": (ctypes.c_int, [_c_void_p, _c_void_p, ctypes.POINTER(_i64)]),
     "gcp_set_lookback_wait_us": (ctypes.c_int, [_i64]),
-    # rows f1 / f2 (gcp_raster.hip)
+    # rows f1 / f2 (gcp_bin.hip, gcp_blend.hip) and what serves rows a5 / a6 around them (gcp_sort.hip, gcp_compact.hip, gcp_walk.hip)
     "gcp_tile_grid": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "gcp_scan_i32_workspace_bytes": (_sz, [_i64]),
     "gcp_exclusive_scan_i32": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _c_void_p, _sz, _c_void_p]),

@@ -38,6 +38,11 @@ __device__ __forceinline__ int wave_incl_scan_i(int v) {
 // host side (defined in gcp_scan.hip)
 int hip_fail(hipError_t e);
 
+// Workspaces are carved into 256-byte aligned pieces: the next piece of `count` elements, `p` moved behind it.
+inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+template <typename T>
+inline T* carve(char*& p, size_t count) { T* a = (T*)p; p += align256(count * sizeof(T)); return a; }
+
 }  // namespace gcp
 
 #define GCP_HIP(call)                                        \

@@ -5,7 +5,7 @@
 // But the list is never arbitrary: `_create_rects` (gs_model.py:480-482 -> Utilities.make_rect_points_parallel,
 // uitility.py:336-366) writes it as a concatenation of row-major boxes, one per Gaussian in depth order, and that
 // structure is enough to avoid the sort: cut the list back into rectangles, bin the rectangles into 16x16 tiles (K ~ 3
-// entries each) and let every pixel walk its tile's list (gcp_pairs_scan_boxes, gcp_raster.hip).  This file does the
+// entries each) and let every pixel walk its tile's list (gcp_pairs_scan_boxes, gcp_walk.hip).  This file does the
 // cutting, for ANY list:
 //   a ROW      is a maximal run of consecutive elements (x, y), (x + 1, y), (x + 2, y), ...
 //   a RECTANGLE is a maximal run of consecutive rows with the same first x and the same length whose y grows by one.
@@ -468,8 +468,6 @@ __global__ __launch_bounds__(256) void k_cut_finish(const int* __restrict__ info
   info8[6] = flags ? 0 : (int)k;
   info8[7] = 0;
 }
-
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace
 

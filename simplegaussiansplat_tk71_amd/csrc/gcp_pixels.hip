@@ -204,8 +204,6 @@ __global__ __launch_bounds__(256) void k_pixels_readout(const unsigned* __restri
   if (WRITE && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) info[0] = off[(i64)w1 * bands];  // the scan's total
 }
 
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct PixelsWs {
   size_t cell, filter, cnt, off, scan, total;
   i64 blocks;

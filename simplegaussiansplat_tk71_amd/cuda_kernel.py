@@ -558,6 +558,29 @@ def mask_zero_T(T):
         return [T[mask], mask]
 
 
+def _bin_sticky(startpoint, endpoint, image_width, image_height):
+    """Bin under the current `tile_capacity`; the overflow word of capture-safe bins is OR-ed into the sticky flag (it
+    survives the call, and every replay of a captured step executes it again)."""
+    bins = _raster.bin_tiles(startpoint, endpoint, int(image_width), int(image_height), capacity=_capacity)
+    if bins.info is not None:
+        flag = _sticky_flag(bins.info.device)
+        torch.maximum(flag, bins.info[1:2], out=flag)
+    return bins
+
+
+def _save_with_bins(ctx, bins, *tensors):
+    """Every tensor goes through save_for_backward (autograd then owns its lifetime and checks it for in-place changes), the
+    three tile arrays last; the node itself keeps only integers."""
+    ctx.bins_meta = (bins.width, bins.height, bins.n_gauss, bins.n_tile_pairs, bins.tiles_x, bins.tiles_y)
+    ctx.save_for_backward(*tensors, bins.tile_off, bins.tile_start, bins.tile_list)
+
+
+def _saved_with_bins(ctx):
+    """-> (the tensors `_save_with_bins` was given, the TileBins)"""
+    *tensors, tile_off, tile_start, tile_list = ctx.saved_tensors
+    return tensors, _raster.TileBins(*ctx.bins_meta, tile_off, tile_start, tile_list)
+
+
 class custom_autograd_grouped_cumprod(torch.autograd.Function):
     """The reference's rasterise-and-blend Function, same name and call signature
     (reference: gs_model.py:477-820; call site gs_model.py:449):
@@ -568,7 +591,7 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
     Inputs are the Gaussians of one camera in depth order.  Instead of expanding them into M
     splat-pixel pairs, sorting, scanning, un-sorting and scatter-adding (gs_model.py:598-624), the
     Gaussians are binned into 16x16 tiles and blended per pixel in one fused kernel
-    (csrc/gcp_raster.hip); backward returns the same four gradients (gs_model.py:820).
+    (csrc/gcp_blend.hip); backward returns the same four gradients (gs_model.py:820).
 
     Differences, all documented in DESIGN.md:
       * `boxsize` and `batch` are accepted and ignored: they exist to chunk the pair list for
@@ -601,26 +624,18 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
                 image_height):
         _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d)
         with torch.no_grad():
-            w, h = int(image_width), int(image_height)
-            bins = _raster.bin_tiles(startpoint, endpoint, w, h, capacity=_capacity)
-            if bins.info is not None:  # sticky: survives the call, and is re-executed by every replay of a captured step
-                flag = _sticky_flag(bins.info.device)
-                torch.maximum(flag, bins.info[1:2], out=flag)
+            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
             image, t_ckpt = _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d,
                                                   with_checkpoints=True)
         # the reference saves its inputs plus per-chunk (unique_rects, T_min, sizes) and recomputes the M-length pair
         # arrays in backward (gs_model.py:691, :786-820); here: the inputs, one transmittance per pixel and 32 list
-        # entries, and the tile lists.  Every tensor goes through save_for_backward (autograd then owns its lifetime and
-        # checks it for in-place changes); the node itself keeps only integers.
-        ctx.bins_meta = (bins.width, bins.height, bins.n_gauss, bins.n_tile_pairs, bins.tiles_x, bins.tiles_y)
-        ctx.save_for_backward(startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, bins.tile_off,
-                              bins.tile_start, bins.tile_list)
+        # entries, and the tile lists.
+        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt)
         return image
 
     @staticmethod
     def backward(ctx, pixel_sum_grad):
-        startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, tile_off, tile_start, tile_list = ctx.saved_tensors
-        bins = _raster.TileBins(*ctx.bins_meta, tile_off, tile_start, tile_list)
+        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt), bins = _saved_with_bins(ctx)
         with torch.no_grad():
             g_mean, g_vinv, g_op, g_l = _raster.blend_backward(
                 bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, pixel_sum_grad
@@ -630,7 +645,7 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
 
 
 class RenderDepth(torch.autograd.Function):
-    """The Function's blend with an expected-depth map, an alpha map and a background colour (csrc/gcp_raster.hip,
+    """The Function's blend with an expected-depth map, an alpha map and a background colour (csrc/gcp_blend.hip,
     k_blend_fwd_depth / k_blend_bwd_depth); see `render`.  Capture-safe and overflow-reporting under `tile_capacity` /
     `GraphedStep` as `custom_autograd_grouped_cumprod`."""
 
@@ -639,23 +654,15 @@ class RenderDepth(torch.autograd.Function):
         _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
         ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
         with torch.no_grad():
-            w, h = int(image_width), int(image_height)
-            bins = _raster.bin_tiles(startpoint, endpoint, w, h, capacity=_capacity)
-            if bins.info is not None:  # sticky, as in custom_autograd_grouped_cumprod
-                flag = _sticky_flag(bins.info.device)
-                torch.maximum(flag, bins.info[1:2], out=flag)
+            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
             image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
                                                                      l_d, depth, background, with_checkpoints=True)
-        ctx.bins_meta = (bins.width, bins.height, bins.n_gauss, bins.n_tile_pairs, bins.tiles_x, bins.tiles_y)
-        ctx.save_for_backward(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, bins.tile_off,
-                              bins.tile_start, bins.tile_list)
+        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt)
         return image, dmap, alpha
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha):
-        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, tile_off, tile_start,
-         tile_list) = ctx.saved_tensors
-        bins = _raster.TileBins(*ctx.bins_meta, tile_off, tile_start, tile_list)
+        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt), bins = _saved_with_bins(ctx)
         want_bg = background is not None and ctx.needs_input_grad[9]
         with torch.no_grad():
             g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(

@@ -1,6 +1,6 @@
 """Tile binning and fused alpha blending on the HIP library.
 
-Host side of csrc/gcp_raster.hip: allocates buffers with torch, passes raw pointers through the C ABI
+Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
 (include/grouped_cumprod_hip.h).  Everything the reference does around its scan in
 `custom_autograd_grouped_cumprod` (reference: gs_model.py:598-663) happens in three launches here:
 bin (f2), blend forward (f1), blend backward (f1).  No CPU path.
@@ -168,58 +168,6 @@ def _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d):
     return start, end, mean_f, vinv, op, col
 
 
-def blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False):
-    """-> image f32[(H+1),(W+1),3] (reference layout, gs_model.py:505); with_checkpoints=True returns
-    (image, t_ckpt), t_ckpt being the per-pixel transmittance checkpoints `blend_backward` restarts from."""
-    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
-    dev = start.device
-    lib = _lib.load()
-    image = torch.empty(bins.height + 1, bins.width + 1, 3, dtype=torch.float32, device=dev)
-    ckpt = None
-    if with_checkpoints:
-        ckpt = torch.empty(lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height), dtype=torch.float32,
-                           device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(
-            lib.gcp_blend_forward(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
-                                  col.data_ptr(), bins.n_gauss, bins.width, bins.height, bins.tile_start.data_ptr(),
-                                  bins.tile_list.data_ptr(), image.data_ptr(), ckpt.data_ptr() if with_checkpoints else None,
-                                  _stream(dev)),
-            "gcp_blend_forward",
-        )
-    return (image, ckpt) if with_checkpoints else image
-
-
-def blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, grad_image):
-    """-> (grad_mean [N,2], grad_variance_inverse [N,2,2], grad_opacity [N,1], grad_l_d [N,3]).
-    `t_ckpt`: the checkpoints `blend_forward(..., with_checkpoints=True)` returned for the same bins and inputs."""
-    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
-    dev = start.device
-    n = bins.n_gauss
-    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
-    shape = (bins.height + 1, bins.width + 1, 3)
-    _require(tuple(gimg.shape) == shape, f"grad_image: expected shape {shape}")
-    lib = _lib.load()
-    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
-    _require(ck.numel() >= lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height),
-             "t_ckpt: too small for these bins (pass what blend_forward(..., with_checkpoints=True) returned)")
-    g_mean = torch.empty(n, 2, dtype=torch.float32, device=dev)
-    g_vinv = torch.empty(n, 2, 2, dtype=torch.float32, device=dev)
-    g_op = torch.empty(n, 1, dtype=torch.float32, device=dev)
-    g_l = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.gcp_blend_backward_workspace_bytes(bins.tile_capacity), dtype=torch.uint8, device=dev)
-        _lib.check(
-            lib.gcp_blend_backward(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
-                                   col.data_ptr(), n, bins.width, bins.height, bins.tile_off.data_ptr(),
-                                   bins.tile_capacity, bins.tile_start.data_ptr(), bins.tile_list.data_ptr(),
-                                   ck.data_ptr(), gimg.data_ptr(), g_mean.data_ptr(), g_vinv.data_ptr(),
-                                   g_op.data_ptr(), g_l.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-            "gcp_blend_backward",
-        )
-    return g_mean, g_vinv, g_op, g_l
-
-
 def _depth_args(depth, background, n, dev):
     z = _dev_tensor(depth, "depth", torch.float32).reshape(-1)
     _require(z.numel() == n, f"depth: {z.numel()} values, expected {n}")
@@ -232,6 +180,93 @@ def _depth_args(depth, background, n, dev):
     return z, bg
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _checkpoint_floats(lib, bins):
+    return lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height)
+
+
+def _blend_forward(bins, params, with_checkpoints, depth=None, background=None, with_depth=False):
+    """Both forward entry points -> (image[, depth_map, alpha], t_ckpt or None)."""
+    start, end, mean_f, vinv, op, col = _params(*params)
+    dev = start.device
+    z, bg = _depth_args(depth, background, start.size(0), dev) if with_depth else (None, None)
+    lib = _lib.load()
+    shape = (bins.height + 1, bins.width + 1)
+    image = torch.empty(*shape, 3, dtype=torch.float32, device=dev)
+    maps = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(2)] if with_depth else []
+    ckpt = torch.empty(_checkpoint_floats(lib, bins), dtype=torch.float32, device=dev) if with_checkpoints else None
+    name = "gcp_blend_forward_depth" if with_depth else "gcp_blend_forward"
+    with torch.cuda.device(dev):
+        _lib.check(
+            getattr(lib, name)(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(), col.data_ptr(),
+                               *((z.data_ptr(), _ptr(bg)) if with_depth else ()), bins.n_gauss, bins.width, bins.height,
+                               bins.tile_start.data_ptr(), bins.tile_list.data_ptr(), image.data_ptr(),
+                               *(m.data_ptr() for m in maps), _ptr(ckpt), _stream(dev)),
+            name,
+        )
+    return (image, *maps, ckpt)
+
+
+def _blend_backward(bins, params, t_ckpt, grad_image, forward_name, depth=None, background=None, grad_maps=None, background_grad=False):
+    """Both backward entry points; grad_maps None: colour only, else (grad_depth, grad_alpha) of the depth call
+    -> (grad_mean, grad_variance_inverse, grad_opacity, grad_l_d[, grad_depth, grad_background])."""
+    with_depth = grad_maps is not None
+    start, end, mean_f, vinv, op, col = _params(*params)
+    dev = start.device
+    n = bins.n_gauss
+    shape = (bins.height + 1, bins.width + 1)
+    if with_depth:
+        z, bg = _depth_args(depth, background, start.size(0), dev)
+        if grad_image is None:
+            grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
+    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
+    _require(tuple(gimg.shape) == shape + (3,), f"grad_image: expected shape {shape + (3,)}")
+    maps = []
+    for t, name in zip(grad_maps or (), ("grad_depth", "grad_alpha")):
+        if t is not None:
+            t = _dev_tensor(t, name, torch.float32)
+            _require(tuple(t.shape) == shape, f"{name}: expected shape {shape}")
+        maps.append(t)
+    lib = _lib.load()
+    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
+    _require(ck.numel() >= _checkpoint_floats(lib, bins),
+             f"t_ckpt: too small for these bins (pass what {forward_name}(..., with_checkpoints=True) returned)")
+    grads = [torch.empty(n, *tail, dtype=torch.float32, device=dev) for tail in ((2,), (2, 2), (1,), (3,))]  # mean, vinv, opacity, l_d
+    name = "gcp_blend_backward_depth" if with_depth else "gcp_blend_backward"
+    with torch.cuda.device(dev):
+        if with_depth:
+            grads += [torch.empty(n, dtype=torch.float32, device=dev), torch.empty(3, dtype=torch.float32, device=dev) if background_grad else None]
+            ws_bytes = lib.gcp_blend_backward_depth_workspace_bytes(bins.tile_capacity, bins.width, bins.height)
+        else:
+            ws_bytes = lib.gcp_blend_backward_workspace_bytes(bins.tile_capacity)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(
+            getattr(lib, name)(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(), col.data_ptr(),
+                               *((z.data_ptr(), _ptr(bg)) if with_depth else ()), n, bins.width, bins.height,
+                               bins.tile_off.data_ptr(), bins.tile_capacity, bins.tile_start.data_ptr(), bins.tile_list.data_ptr(),
+                               ck.data_ptr(), gimg.data_ptr(), *(_ptr(t) for t in maps), *(_ptr(g) for g in grads),
+                               ws.data_ptr(), ws.numel(), _stream(dev)),
+            name,
+        )
+    return tuple(grads)
+
+
+def blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False):
+    """-> image f32[(H+1),(W+1),3] (reference layout, gs_model.py:505); with_checkpoints=True returns
+    (image, t_ckpt), t_ckpt being the per-pixel transmittance checkpoints `blend_backward` restarts from."""
+    image, ckpt = _blend_forward(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), with_checkpoints)
+    return (image, ckpt) if with_checkpoints else image
+
+
+def blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, grad_image):
+    """-> (grad_mean [N,2], grad_variance_inverse [N,2,2], grad_opacity [N,1], grad_l_d [N,3]).
+    `t_ckpt`: the checkpoints `blend_forward(..., with_checkpoints=True)` returned for the same bins and inputs."""
+    return _blend_backward(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward")
+
+
 def blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background=None,
                         with_checkpoints=False):
     """`blend_forward` that also returns the expected-depth and alpha maps and composites a background colour
@@ -240,27 +275,8 @@ def blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opac
     image = sum_k w_k l_k + T_N * background.  `depth`: [N] per Gaussian; `background`: float[3] on the device (no host
     read; may change between replays of a captured graph) or None = black, the image then bit for bit `blend_forward`'s.
     -> (image f32[H+1, W+1, 3], depth_map f32[H+1, W+1], alpha f32[H+1, W+1]) [+ t_ckpt]."""
-    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
-    dev = start.device
-    z, bg = _depth_args(depth, background, start.size(0), dev)
-    lib = _lib.load()
-    image = torch.empty(bins.height + 1, bins.width + 1, 3, dtype=torch.float32, device=dev)
-    dmap = torch.empty(bins.height + 1, bins.width + 1, dtype=torch.float32, device=dev)
-    alpha = torch.empty(bins.height + 1, bins.width + 1, dtype=torch.float32, device=dev)
-    ckpt = None
-    if with_checkpoints:
-        ckpt = torch.empty(lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height), dtype=torch.float32,
-                           device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(
-            lib.gcp_blend_forward_depth(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
-                                        col.data_ptr(), z.data_ptr(), bg.data_ptr() if bg is not None else None, bins.n_gauss,
-                                        bins.width, bins.height, bins.tile_start.data_ptr(), bins.tile_list.data_ptr(),
-                                        image.data_ptr(), dmap.data_ptr(), alpha.data_ptr(),
-                                        ckpt.data_ptr() if with_checkpoints else None, _stream(dev)),
-            "gcp_blend_forward_depth",
-        )
-    return (image, dmap, alpha, ckpt) if with_checkpoints else (image, dmap, alpha)
+    out = _blend_forward(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), with_checkpoints, depth, background, True)
+    return out if with_checkpoints else out[:3]
 
 
 def blend_backward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, grad_image,
@@ -270,45 +286,8 @@ def blend_backward_depth(bins, startpoint, endpoint, mean, variance_inverse, opa
     grad_l_d [N,3], grad_depth [N], grad_background [3] or None).  Dropped pairs get zero gradients; where T_N is 0 the
     background and alpha terms have none.  `background_grad`: also return dL/dbackground = sum_p grad_image(p) T_N(p)
     (summed in a fixed order).  `grad_image` None: zero."""
-    start, end, mean_f, vinv, op, col = _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d)
-    dev = start.device
-    n = bins.n_gauss
-    z, bg = _depth_args(depth, background, start.size(0), dev)
-    shape = (bins.height + 1, bins.width + 1)
-    if grad_image is None:
-        grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
-    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
-    _require(tuple(gimg.shape) == shape + (3,), f"grad_image: expected shape {shape + (3,)}")
-    maps = []
-    for t, name in ((grad_depth, "grad_depth"), (grad_alpha, "grad_alpha")):
-        if t is not None:
-            t = _dev_tensor(t, name, torch.float32)
-            _require(tuple(t.shape) == shape, f"{name}: expected shape {shape}")
-        maps.append(t)
-    lib = _lib.load()
-    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
-    _require(ck.numel() >= lib.gcp_blend_checkpoint_floats(bins.tile_capacity, bins.width, bins.height),
-             "t_ckpt: too small for these bins (pass what blend_forward_depth(..., with_checkpoints=True) returned)")
-    g_mean = torch.empty(n, 2, dtype=torch.float32, device=dev)
-    g_vinv = torch.empty(n, 2, 2, dtype=torch.float32, device=dev)
-    g_op = torch.empty(n, 1, dtype=torch.float32, device=dev)
-    g_l = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    g_z = torch.empty(n, dtype=torch.float32, device=dev)
-    g_bg = torch.empty(3, dtype=torch.float32, device=dev) if background_grad else None
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.gcp_blend_backward_depth_workspace_bytes(bins.tile_capacity, bins.width, bins.height), dtype=torch.uint8,
-                         device=dev)
-        _lib.check(
-            lib.gcp_blend_backward_depth(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
-                                         col.data_ptr(), z.data_ptr(), bg.data_ptr() if bg is not None else None, n, bins.width,
-                                         bins.height, bins.tile_off.data_ptr(), bins.tile_capacity, bins.tile_start.data_ptr(),
-                                         bins.tile_list.data_ptr(), ck.data_ptr(), gimg.data_ptr(),
-                                         *(t.data_ptr() if t is not None else None for t in maps),
-                                         g_mean.data_ptr(), g_vinv.data_ptr(), g_op.data_ptr(), g_l.data_ptr(), g_z.data_ptr(),
-                                         g_bg.data_ptr() if g_bg is not None else None, ws.data_ptr(), ws.numel(), _stream(dev)),
-            "gcp_blend_backward_depth",
-        )
-    return g_mean, g_vinv, g_op, g_l, g_z, g_bg
+    return _blend_backward(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward_depth",
+                           depth, background, (grad_depth, grad_alpha), background_grad)
 
 
 def exclusive_scan_i32(x):

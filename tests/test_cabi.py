@@ -157,14 +157,15 @@ def test_walk_compaction_and_blend_kernels_use_no_scratch(tmp_path):
 
     from simplegaussiansplat_tk71_amd import _build
 
-    src = [s for s in _build.SRCS if s.endswith("gcp_raster.hip")][0]
-    out = tmp_path / "raster.s"
     flags = [f for f in _build.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
-    res = subprocess.run([_build.find_hipcc(), *flags, "-I", _build.INCLUDE, "-S", "--cuda-device-only", "-o", str(out), src],
-                         capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", text)
+    kernels = []  # of all the tile-stage sources together
+    for name in ("gcp_bin.hip", "gcp_blend.hip", "gcp_sort.hip", "gcp_walk.hip", "gcp_compact.hip"):
+        src = [s for s in _build.SRCS if s.endswith(name)][0]
+        out = tmp_path / (name + ".s")
+        res = subprocess.run([_build.find_hipcc(), *flags, "-I", _build.INCLUDE, "-S", "--cuda-device-only", "-o", str(out), src],
+                             capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr[-2000:]
+        kernels += re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", out.read_text())
     seen = {frag: [k for k in kernels if frag in k[0]] for frag in ("k_pairs_scan_boxes", "k_compact", "k_blend_bwd", "k_blend_fwd", "k_sort_scatter2")}
     # the walk: 3 modes x 2 address forms x 3 outputs (inclusive, inclusive + zero counts, final values + keep mask);
     # k_compact<VEC, WRITE> x 4 and k_compact_kept<VEC> x 2

@@ -1,4 +1,4 @@
-"""Rows f1/f2: tile binning + fused blend (csrc/gcp_raster.hip) vs the reference's own Function outputs
+"""Rows f1/f2: tile binning + fused blend (csrc/gcp_bin.hip, csrc/gcp_blend.hip) vs the reference's own Function outputs
 (tests/golden/function_golden.npz) and vs the dense autograd oracle (oracle/dense_render.py)."""
 import os
 
@@ -434,7 +434,7 @@ def test_gaussians_behind_an_opaque_stack_get_accurate_gradients(device):
     """60 layers of opacity 0.6 over the whole image leave T ~ 1e-24 for the 40 Gaussians behind them.  The reference's
     reverse scan (gs_model.py:716-722) gives those their true, tiny gradients; a backward that forms suffix sums as
     (pixel total) - (prefix) hands them ~1e-7 of the total instead — noise that Adam normalises into full-size steps.
-    Here every gradient term is T_k times a bounded quantity (csrc/gcp_raster.hip, k_blend_bwd), so the hidden
+    Here every gradient term is T_k times a bounded quantity (csrc/gcp_blend.hip, k_blend_bwd), so the hidden
     Gaussians' gradients must be right to a RELATIVE 1e-3 although they are ~1e-20."""
     w = h = 31
     n_front, n_back = 60, 40

@@ -47,7 +47,7 @@ def test_depth_blend_kernels_use_no_scratch_and_keep_six_waves(tmp_path):
     from simplegaussiansplat_tk71_amd import _build
 
     found = {}
-    for name in ("gcp_raster.hip", "gcp_project.hip"):
+    for name in ("gcp_bin.hip", "gcp_blend.hip", "gcp_sort.hip", "gcp_walk.hip", "gcp_compact.hip", "gcp_project.hip"):
         src = [s for s in _build.SRCS if s.endswith(name)][0]
         out = tmp_path / (name + ".s")
         flags = [f for f in _build.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]

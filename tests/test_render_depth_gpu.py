@@ -1,4 +1,4 @@
-"""Depth, alpha and background from the fused blend (cuda_kernel.render, csrc/gcp_raster.hip k_blend_fwd_depth /
+"""Depth, alpha and background from the fused blend (cuda_kernel.render, csrc/gcp_blend.hip k_blend_fwd_depth /
 k_blend_bwd_depth) and through the model (GS_model_with_param.render) against a dense fp64 oracle written here."""
 import math
 import os
