@@ -349,7 +349,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   // descriptor set of this launch (parity of the workspace's launch counter); a scalar load issued first
   unsigned long long* const desc = a.desc_sets + (a.hdr[kHdrEpoch] & 1u);  // tile t at desc[2 t]
 
-  // backward: this wave's memory range and the groups at its two ends (wave-uniform loads, issued before the tile's data)
+  // backward: this wave's memory range (the groups at its two ends are looked up behind the issue of the tile's data)
   const int wu = __builtin_amdgcn_readfirstlane(w);
   i64 wlo = 0, whi = -1;
   int ga = 0, gb = -1;
@@ -357,7 +357,6 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     wlo = base + kTile - (i64)(wu + 1) * WT;
     whi = base + kTile - 1 - (i64)wu * WT;
     if (whi > n - 1) whi = n - 1;
-    if (wlo <= whi) { ga = a.key[wlo]; gb = a.key[whi]; }
   }
 
   // ---- issue all loads of this lane ------------------------------------
@@ -421,6 +420,13 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     if constexpr (BWD) xp[r] = to_scan_order<REV>(xp[r]);
   }
 
+  // backward: the groups at the two ends of the wave's range, two wave-uniform (scalar) loads.  Issued here and not in
+  // front of the tile's loads: the compiler waits for them together with the kernel arguments, so in front they cost
+  // the wave a whole round trip with nothing of its own in flight; behind, that round trip overlaps the data's.
+  if constexpr (BWD) {
+    if (wlo <= whi) { ga = a.key[wlo]; gb = a.key[whi]; }
+  }
+
   // key of the element just before this wave's chunk in scan order
   const i64 pn = REV ? (base + kTile - (i64)w * WT) : (base + (i64)w * WT - 1);
   // (both bounds in both directions: in a partial tile the waves whose chunk lies wholly past the end of the array must not
@@ -433,6 +439,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   // look-back chunk 0 (wave 0 only): issued now so its latency overlaps
   const bool do_lb = !FIXUP && !INPLACE && (w == 0) && (lt > 0);  // (in place: see below)
   float4_t lbv = {id, id, id, id};
+  float4_t lbc = {id, id, id, id};  // backward: the second factor, multiplied in where the chunk is used (a product taken
+                                    // here is waited for here, and with it every load of the tile issued before it)
   int4_t lbk = {0, 0, 0, 0};
   i64 lbp = 0;
   if (do_lb) {
@@ -442,9 +450,12 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       if constexpr (BWD) lbv = ld4<ALIGNED>(a.in2 + lbp) * ld4<ALIGNED>(a.in1 + lbp);
       else if constexpr (INDEXED) lbv = ld4_indexed<ALIGNED, false>(a.in0, a.index, lbp, lb_ix);
       else lbv = ld4<ALIGNED>(a.in0 + lbp);
+    } else if (BWD && base + kTile + 256 <= n) {  // the chunk lies wholly inside the array: two vector loads, not eight guarded ones
+      lbv = ld4<ALIGNED>(a.in2 + lbp);
+      lbc = ld4<ALIGNED>(a.in1 + lbp);
     } else {
       if constexpr (!BWD) lbk = ld4_guard(a.key, lbp, n, 0);
-      if constexpr (BWD) lbv = ld4_guard(a.in2, lbp, n, 0.0f) * ld4_guard(a.in1, lbp, n, 0.0f);
+      if constexpr (BWD) { lbv = ld4_guard(a.in2, lbp, n, 0.0f); lbc = ld4_guard(a.in1, lbp, n, 0.0f); }
       else if constexpr (INDEXED) lbv = ld4_indexed_guard(a.in0, a.index, lbp, n, id, lb_ix);
       else lbv = ld4_guard(a.in0, lbp, n, id);
     }
@@ -597,6 +608,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
         const bool more = REV ? (base + kTile + (i64)(j + 1) * 256 < n) : (base - (i64)(j + 1) * 256 > 0);
         return !more;             // reached the end of the array: resolved
       };
+      if constexpr (BWD) lbv = lbv * lbc;
       bool done = process(lbv, lbk, lbp, 0);
       // A group that already spans the 256 elements behind the tile AND this wave's whole 1024-element share is long:
       // stop reading raw inputs (up to three more dependent round trips that would most likely end at the window's
