@@ -76,7 +76,9 @@ constexpr int kThreads = 256;      // 4 waves
 constexpr int kWaves = 4;
 constexpr int kRows = 4;           // 16-byte vectors per lane per array
 constexpr int kTile = 1024 * kRows;
-constexpr int kLbBatch = 5;        // look-back chunks fetched per dependent round trip after the first
+constexpr int kLbBatch = 5;        // look-back chunks fetched per dependent round trip after the first ...
+constexpr int kLbBatchBwd = 3;     // ... in the cumprod backward: two factors per chunk, and five chunks in flight were the kernel's
+                                   // register peak (146 VGPRs, three waves per SIMD); three fit four waves without scratch
 constexpr int kLbChunks = ((kTile / 256 - 1) / kLbBatch) * kLbBatch + 1;  // window in 256-element chunks (16 = one tile at kRows 4)
 constexpr int kFixBlocks = 256;     // upper bound of the fallback kernel's grid (two-pass mode)
 constexpr int kFixBlocksQuiet = 32; // ... when the descriptor tree is on and the kernel normally finds nothing to do
@@ -103,12 +105,14 @@ constexpr int kDescWaitUs = 200;    // default patience of the descriptor walk (
 
 static_assert(kLbChunks * 256 == kTile, "the raw look-back window is exactly the previous tile (the descriptor walk starts at the tile before it)");
 static_assert((kLbChunks - 1) % kLbBatch == 0, "chunks after the first are fetched kLbBatch at a time");
+static_assert((kLbChunks - 1) % kLbBatchBwd == 0, "chunks after the first are fetched kLbBatchBwd at a time in the backward");
 
 template <int MODE>
 struct Mode {
   static constexpr bool kMul = (MODE == M_CUMPROD_FWD);
   static constexpr bool kRev = (MODE == M_CUMPROD_BWD || MODE == M_CUMSUM_REV);
   static constexpr bool kBwd = (MODE == M_CUMPROD_BWD);
+  static constexpr int kBatch = kBwd ? kLbBatchBwd : kLbBatch;  // chunks are processed one by one in the same order either way
 };
 
 template <bool MUL>
@@ -574,8 +578,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
 
   // ---- look-back (wave 0): carry entering the tile -------------------------
   // Chunk 0 (256 elements) was loaded speculatively with the tile.  If the group
-  // reaches further back, chunks are fetched kLbBatch at a time (one dependent
-  // round trip per batch) up to one full tile.
+  // reaches further back, chunks are fetched MD::kBatch at a time (one dependent
+  // round trip per batch; five, three in the cumprod backward) up to one full tile.
   if (w == 0) {
     float tc = FIXUP ? fix_carry : id;
     int unresolved = 0;
@@ -616,12 +620,12 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       bool wave_headless = true;
 #pragma unroll
       for (int r = 0; r < kRows; ++r) wave_headless = wave_headless && (hmask[r] == 0ull);
-      for (int j = 1; !done && !wave_headless && j < kLbChunks; j += kLbBatch) {
-        float4_t cv[kLbBatch];
-        int4_t ck[kLbBatch];
-        i64 cp[kLbBatch];
+      for (int j = 1; !done && !wave_headless && j < kLbChunks; j += MD::kBatch) {
+        float4_t cv[MD::kBatch];
+        int4_t ck[MD::kBatch];
+        i64 cp[MD::kBatch];
 #pragma unroll
-        for (int c = 0; c < kLbBatch; ++c) {
+        for (int c = 0; c < MD::kBatch; ++c) {
           cp[c] = REV ? (base + kTile + (i64)(j + c) * 256 + lane * 4) : (base - ((i64)(j + c) * 256 + lane * 4 + 4));
           if (!REV) {
             ck[c] = ld4<ALIGNED>(a.key + cp[c]);
@@ -637,7 +641,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
           }
         }
 #pragma unroll
-        for (int c = 0; c < kLbBatch; ++c) {
+        for (int c = 0; c < MD::kBatch; ++c) {
           if (!done) done = process(cv[c], ck[c], cp[c], j + c);
         }
       }
@@ -828,10 +832,19 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
 
 }
 
-// Forward modes: six blocks per CU (<= 80 VGPRs), which the rare descriptor walk must not cost; the reverse modes are
-// left to the register allocator (the backward holds three arrays per element and runs at three blocks per CU).
+// Forward modes: six blocks per CU (<= 80 VGPRs), which the rare descriptor walk must not cost.  The cumprod backward holds
+// three arrays per element: four blocks per CU (<= 128 VGPRs, no scratch: tests/test_bwd_occupancy.py), so that a tile
+// waiting for its group ends leaves three others' loads in flight and not two (cfg3: 457 -> 436 us; a launch whose waves ALL
+// take the key fall-back pays 2-3 % for it: profiles/r08_bwd_occupancy.md).  The reverse sum, the indexed and the
+// in-place scans are left to the register allocator.
+template <int MODE>
+constexpr int waves_per_simd(bool indexed, bool inplace, bool upper) {
+  if (Mode<MODE>::kBwd) return 4;
+  if (Mode<MODE>::kRev || indexed || inplace) return upper ? 8 : 1;
+  return 6;
+}
 template <int MODE, bool ALIGNED, bool CARRY, bool INDEXED = false, bool INPLACE = false>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((Mode<MODE>::kRev || INDEXED || INPLACE) ? 1 : 6, (Mode<MODE>::kRev || INDEXED || INPLACE) ? 8 : 6)))
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(waves_per_simd<MODE>(INDEXED, INPLACE, false), waves_per_simd<MODE>(INDEXED, INPLACE, true))))
 void gcp_scan_main(const ScanArgs a) {
   __shared__ float s_wv[kWaves];
   __shared__ int s_wf[kWaves + 2];
@@ -922,7 +935,14 @@ __device__ __forceinline__ void grid_barrier(unsigned* ctr, unsigned target) {
 // Every block, whatever it finds, also (i) clears its share of the OTHER descriptor set over the range its last user
 // wrote — the set the next launch on this workspace will publish into — and (ii) counts itself done; the last block
 // to finish advances the launch counter, which flips the sets.  Nobody reads the other set or the counter's parity
-// after that point in this launch, so neither needs a barrier.
+// in this launch, so neither needs a barrier.
+// The quiet path is latency and nothing else, so the count and the clear are ONE sweep that waits once: a thread's
+// descriptors are fetched kSweep at a time as 16-byte loads of both sets' words, whose addresses need nothing from the
+// header (the launch counter is waited for together with them, not in front of them); the clears, plain stores, are
+// issued behind the loads and before their first use.
+constexpr int kSweep = 8;  // one round trip serves 2048 tiles per block: 65 536 tiles on the quiet grid
+typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
+
 template <int MODE, bool CARRY, bool INDEXED = false>
 __global__ __launch_bounds__(kThreads) void gcp_fallback(const ScanArgs a) {
   typedef Mode<MODE> MD;
@@ -935,28 +955,68 @@ __global__ __launch_bounds__(kThreads) void gcp_fallback(const ScanArgs a) {
   __shared__ int s_tile[64];
   __shared__ float s_carry;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const unsigned epoch = a.hdr[kHdrEpoch];
-  const unsigned set = epoch & 1u;
-  unsigned long long* const desc = a.desc_sets + set;
-  const bool any = a.hdr[kHdrAnyUnresolved] != 0u;  // the same for every block: written by the main kernel only
-  const i64 per = (a.ntiles + gridDim.x - 1) / gridDim.x;
+  // (tile and entry counts fit 31 bits, launch_scan: 32-bit divisions)
+  const unsigned per = ((unsigned)a.ntiles + gridDim.x - 1u) / gridDim.x;
   const i64 r0 = (i64)blockIdx.x * per;
   const i64 r1 = (r0 + per < a.ntiles) ? (r0 + per) : a.ntiles;
+  // {set 0, set 1} of the block's tiles r0 + b + k * kThreads, k < kSweep; past the block's range tile 0 is read and not
+  // counted: loads without branches (the grid has at most ntiles blocks, so tile 0 exists)
+  auto fetch = [&](u64x2_t (&d)[kSweep], i64 b) {
+#pragma unroll
+    for (int k = 0; k < kSweep; ++k) {
+      const i64 t = r0 + b + k * kThreads;
+      d[k] = *(const u64x2_t*)(a.desc_sets + 2 * (t < r1 ? t : 0));
+    }
+  };
+  u64x2_t d[kSweep];
+  fetch(d, tid);
+  // every header word the kernel needs, read at once (the other set's size is a word of its own per set)
+  const unsigned epoch = a.hdr[kHdrEpoch];
+  const unsigned tiles0 = a.hdr[kHdrTiles], tiles1 = a.hdr[kHdrTiles + 1];
+  const bool any = a.hdr[kHdrAnyUnresolved] != 0u;  // the same for every block: written by the main kernel only
+  const unsigned set = epoch & 1u;
+  unsigned long long* const desc = a.desc_sets + set;
+  unsigned long long* const other = a.desc_sets + (set ^ 1u);
+  const unsigned n_other = set ? tiles0 : tiles1;
+  const unsigned oper = (n_other + gridDim.x - 1u) / gridDim.x;
+  const i64 z0 = (i64)blockIdx.x * oper;
+  const i64 z1 = (z0 + oper < (i64)n_other) ? (z0 + oper) : (i64)n_other;
 
-  // introspection counters of this launch, from the flags of the level-0 descriptors
+  // the sweep: introspection counters of this launch from the flags of the block's level-0 descriptors [r0, r1), and
+  // the block's share [z0, z1) of the other set cleared
   if (tid == 0) { s_any = 0; s_tree = 0; }
   __syncthreads();
   {
     int mine = 0, tree = 0;
-    for (i64 t = r0 + tid; t < r1; t += kThreads) {
-      const unsigned fl = (unsigned)(desc[2 * t] >> 32);
-      mine += (int)((fl >> 1) & 1u);
-      tree += (int)((fl >> 16) & 1u);
+    auto clear = [&](i64 b) {
+#pragma unroll
+      for (int k = 0; k < kSweep; ++k) {
+        const i64 z = z0 + b + k * kThreads;
+        if (z < z1) other[2 * z] = 0ull;
+      }
+    };
+    auto count = [&](i64 b) {
+#pragma unroll
+      for (int k = 0; k < kSweep; ++k) {
+        const unsigned fl = (r0 + b + k * kThreads < r1) ? (unsigned)((set ? d[k].y : d[k].x) >> 32) : 0u;
+        mine += (int)((fl >> 1) & 1u);
+        tree += (int)((fl >> 16) & 1u);
+      }
+    };
+    // the first pass, straight-line: the clears go out while the loads issued above are still in flight
+    clear(tid);
+    count(tid);
+    // further passes (more than 2048 tiles or entries per block); one that has only clears left issues no loads
+    for (i64 b = (i64)kSweep * kThreads; r0 + b < r1 || z0 + b < z1; b += (i64)kSweep * kThreads) {  // block-uniform
+      const bool more = r0 + b < r1;
+      if (more) fetch(d, b + tid);
+      clear(b + tid);
+      if (more) count(b + tid);
     }
     if (mine) atomicAdd(&s_any, mine);
     if (tree) atomicAdd(&s_tree, tree);
   }
-  __syncthreads();
+  __syncthreads();  // the counts are complete; every thread's clears are issued before the block reports itself done
   if (tid == 0 && s_tree) atomicAdd(a.hdr + kHdrDescResolved, (unsigned)s_tree);
   if (tid == 0 && s_any) atomicAdd(a.hdr + kHdrUnresolved, (unsigned)s_any);
 
@@ -1003,13 +1063,6 @@ __global__ __launch_bounds__(kThreads) void gcp_fallback(const ScanArgs a) {
     }
   }
 
-  unsigned long long* const other = a.desc_sets + (set ^ 1u);
-  const i64 n_other = (i64)a.hdr[kHdrTiles + (set ^ 1u)];
-  const i64 oper = (n_other + gridDim.x - 1) / gridDim.x;
-  const i64 z0 = (i64)blockIdx.x * oper;
-  const i64 z1 = (z0 + oper < n_other) ? (z0 + oper) : n_other;
-  for (i64 t = z0 + tid; t < z1; t += kThreads) other[2 * t] = 0ull;
-  __syncthreads();  // every thread's clears are issued before the block reports itself done
   if (tid == 0) {
     __threadfence();
     if (atomicAdd(a.hdr + kHdrDone, 1u) == gridDim.x - 1) {
