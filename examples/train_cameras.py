@@ -8,6 +8,10 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py                         # synthetic scene (the default; runs anywhere)
     python examples/train_cameras.py --colmap DIR            # DIR/sparse/0/{cameras,images,points3D}.bin + DIR/images/
     python examples/train_cameras.py --background random     # render over a random colour per step (or "1,1,1": white)
+    python examples/train_cameras.py --sh-degree 3 --sh-frame world --sh-every 100 --save-ply scene.ply
+                                                             # degree-3 colour on world-space directions, one degree more
+                                                             # every 100 steps, saved as a standard 3DGS .ply
+    python examples/train_cameras.py --load-ply scene.ply --sh-frame world      # resume from such a file
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -67,12 +71,16 @@ def load_colmap(root, device):
 
 def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2, opacity_init=0.1, neighbours=3,
           densify_from_iter=500, densify_until_iter=15000, densification_interval=100, opacity_reset_interval=3000,
-          reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None):
+          reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
+          sh_frame="camera", sh_every=0, save_ply=None, load_ply=None):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
     generator: the same on every rank); the images are then rendered over it (GS_model_with_param.render) and, where
-    `target_alpha` (B, 1, H, W) is given, the targets composited over it too."""
+    `target_alpha` (B, 1, H, W) is given, the targets composited over it too.
+    `sh_degree` (0..3) and `sh_frame` ("camera" / "world"): the appearance model (gs_model.camera_inputs); `sh_every` N > 0:
+    start at degree 0 and activate one more every N iterations.  `load_ply`: start from that scene file instead of `start`
+    (its degree replaces `sh_degree`); `save_ply`: write the trained scene there (rank 0)."""
     if isinstance(background, str) and background != "random":
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
@@ -82,7 +90,11 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     q[:, 3] = 1  # identity rotation, (x, y, z, w) (gs_control.py:113-114)
     scale = torch.log(gm.mean_neighbour_distance(neighbours, start))
     opacity = torch.full((n, 1), math.log(opacity_init / (1 - opacity_init)), device=dev)
-    model = gm.GS_model_with_param(start.clone(), q, scale, opacity)
+    sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None}
+    if load_ply is not None:
+        model = gm.GS_model_with_param.from_ply(load_ply, dev, **sh)
+    else:
+        model = gm.GS_model_with_param(start.clone(), q, scale, opacity, L_max=sh_degree, **sh)
     data = gm.GS_dataset(P, K, wh, list(range(P.shape[0])))
     extent = data.get_camera_extent()
     gen = torch.Generator().manual_seed(seed)
@@ -122,6 +134,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             iteration += 1
             losses.append(float(loss.detach()))
             model.set_mean_lr(iteration)
+            if sh_every and iteration % sh_every == 0:
+                model.oneup_sh_degree()
             if densify_from_iter <= iteration <= densify_until_iter and iteration % densification_interval == 0:
                 model.densify_and_prune(extent)
             if opacity_reset_interval and iteration % opacity_reset_interval == 0:
@@ -133,6 +147,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     if dev.type == "cuda":
         torch.cuda.synchronize()
     log(f"{iteration} iterations in {time.time() - t0:.1f} s")
+    if save_ply is not None and rank == 0:
+        model.save_ply(save_ply)
     return model, losses
 
 
@@ -147,6 +163,12 @@ if __name__ == "__main__":
     ap.add_argument("--densify-from", type=int, default=500)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend under torchrun (nccl = RCCL; gloo to rehearse on one GPU)")
     ap.add_argument("--background", default=None, help='"random" (a colour per step) or "r,g,b"; default: black')
+    ap.add_argument("--sh-degree", type=int, choices=(0, 1, 2, 3), default=2, help="SH degree of the colour")
+    ap.add_argument("--sh-frame", choices=("camera", "world"), default="camera",
+                    help="directions the SH basis is evaluated on; world = the convention of other 3DGS renderers")
+    ap.add_argument("--sh-every", type=int, default=0, metavar="N", help="start at degree 0, one degree more every N iterations (0: off)")
+    ap.add_argument("--save-ply", default=None, metavar="PATH", help="write the trained scene as a standard 3DGS .ply")
+    ap.add_argument("--load-ply", default=None, metavar="PATH", help="start from a 3DGS .ply instead of the point cloud")
     a = ap.parse_args()
     background = a.background if a.background in (None, "random") else tuple(float(v) for v in a.background.split(","))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -165,7 +187,8 @@ if __name__ == "__main__":
     else:
         start, P, K, wh, targets = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device)
     _, losses = train(start, P, K, wh, targets, iterations=a.iterations, densify_from_iter=a.densify_from, rank=rank, world=world,
-                      log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas)
+                      log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas, sh_degree=a.sh_degree,
+                      sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

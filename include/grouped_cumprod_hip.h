@@ -519,8 +519,9 @@ int gcp_pixel_lists_fill(const int32_t* start_xy, const int32_t* end_xy, int64_t
 /* ---- the caller's camera projection, fused ----------------------------------------------
  * One camera of GS_model_with_param.forward up to the Function call (reference: gs_model.py:289-365, :404-425;
  * helpers uitility.py:231-287, :431-462): world->camera, pinhole projection, pixel covariance J W S W^T J^T + 1e-6 I,
- * 3-sigma box from its eigen-decomposition, its inverse, SH colour (degree <= 2, coefficients [n_basis][3] per
- * Gaussian), sigmoid opacity, the cull test and the clamped integer box.
+ * 3-sigma box from its eigen-decomposition, its inverse, SH colour (real spherical harmonics in the usual 3DGS order and
+ * sign, sh_degree 0..3, coefficients [n_basis][3] per Gaussian with n_basis >= (sh_degree + 1)^2: rows above the active
+ * degree are stored, not read, and get zero gradients), sigmoid opacity, the cull test and the clamped integer box.
  *   cam_P float[12] = [R|t] row major, cam_K float[9] row major, both in device memory;
  *   box_clamp = the float the 3-sigma half extents are clamped to before truncation (gs_model.py:364-365).
  * gcp_project_forward writes, in the Gaussians' own order: record float[n_gauss][16] (16-byte aligned; opaque, read
@@ -536,7 +537,14 @@ int gcp_pixel_lists_fill(const int32_t* start_xy, const int32_t* end_xy, int64_t
  * each, all rows written (zeros where row_of < 0), from those of (Sigma'^-1, opacity, l_d) in list order.
  * gcp_project_gather_depth / gcp_project_backward_depth: the same plus each Gaussian's camera-space depth z (the
  * positive depth the sort key holds; 0 for a culled entry of the capture-safe form) in list order, and its gradient
- * grad_depth [n_kept] (dz/dmean = row 2 of [R|t]). */
+ * grad_depth [n_kept] (dz/dmean = row 2 of [R|t]).
+ * gcp_project_forward_sh / gcp_project_backward_sh: the same with the direction the SH basis is evaluated on chosen by
+ * sh_frame: 0 = -t/|t| in camera coordinates (what the entry points above use: the reference's call site,
+ * gs_model.py:335-338), 1 = the world-space unit vector from the camera centre to the Gaussian, R^T t/|t| (R = the
+ * rotation of [R|t], taken to be orthonormal) — the convention of other 3DGS renderers; the colour then does not change
+ * when the camera rolls about its axis.  gcp_project_backward_sh serves both backwards: grad_depth may be NULL (no depth
+ * gradient).  Every entry point returns GCP_ERR_INVALID_ARGUMENT, before any HIP call, for sh_degree outside 0..3,
+ * n_basis < (sh_degree + 1)^2 or sh_frame outside {0, 1}; n_gauss == 0 is a no-op after those checks. */
 int gcp_project_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
                         const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
                         int32_t n_basis, int32_t width, int32_t height, float box_clamp, float* record, int32_t* sort_key,
@@ -557,6 +565,16 @@ int gcp_project_backward_depth(const float* mean, const float* quat_xyzw, const 
                                int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                                const float* grad_l_d, const float* grad_depth, float* grad_mean, float* grad_quat,
                                float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream);
+int gcp_project_forward_sh(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                           const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                           int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float* record,
+                           int32_t* sort_key, uint8_t* keep, int32_t* row_of, void* stream);
+int gcp_project_backward_sh(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                            const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                            int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv,
+                            const float* grad_alpha, const float* grad_l_d, const float* grad_depth /* may be NULL */,
+                            float* grad_mean, float* grad_quat, float* grad_log_scale, float* grad_opacity_logit,
+                            float* grad_sh_coeff, void* stream);
 
 /* ---- the caller's training loss, fused ---------------------------------------------------
  * (1 - lambda) * mean|a - b| + lambda * (1 - mean SSIM(a, b)) of gs_control.py:180-182 (kornia.metrics.ssim with an

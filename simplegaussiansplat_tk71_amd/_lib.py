@@ -114,6 +114,9 @@ SIGNATURES = {
     "gcp_project_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 10),
     "gcp_project_gather_depth": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
     "gcp_project_backward_depth": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 11),
+    # the same with the SH direction's frame chosen (0 camera, 1 world); the backward's grad_depth may be NULL
+    "gcp_project_forward_sh": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, ctypes.c_float] + [_c_void_p] * 5),
+    "gcp_project_backward_sh": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 11),
 }
 
 ABI_VERSION = 4

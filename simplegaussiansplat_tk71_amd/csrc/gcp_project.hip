@@ -6,9 +6,17 @@
 // k_project_fwd writes, in the Gaussians' own order, everything the Function needs of it for one camera;
 // k_project_bwd recomputes the chain in registers and turns (dL/dSigma'^-1, dL/dopacity, dL/dl_d) into the
 // gradients of (mean, quaternion, log-scale, opacity logit, SH coefficients).  HBM bound: 152 B in, 77 B out per
-// Gaussian forward; no LDS, no cross-lane traffic.  Depth order: the forward also emits a 31-bit sort key per
-// Gaussian (bits of the positive depth; culled last) for gcp_sort_pairs_u32, and k_project_gather unpacks the
+// Gaussian forward at 9 SH coefficients; no cross-lane traffic.  Depth order: the forward also emits a 31-bit sort key
+// per Gaussian (bits of the positive depth; culled last) for gcp_sort_pairs_u32, and k_project_gather unpacks the
 // kept records in that order.
+//
+// Appearance: real spherical harmonics up to degree 3 in the usual 3DGS order and sign, evaluated on the direction
+// -t/|t| in camera coordinates (the reference's call site, gs_model.py:335-338; the default) or on the world-space unit
+// vector from the camera centre to the Gaussian, W^T t/|t| (sh_frame 1).  Both are compile-time: a 256-thread block
+// stages 10 + 3 n_basis floats per Gaussian in LDS, 37 888 B at 9 coefficients (four blocks per CU, 4 waves per SIMD,
+// <= 128 VGPRs) and 59 392 B at 16 (two blocks per CU, 2 waves per SIMD, <= 256 VGPRs) — so degree <= 2 in the camera
+// frame runs the kernels it always ran (k_project_fwd, k_project_bwd, k_project_bwd_depth) and only degree 3 pays for the
+// sixteen-term basis in registers (k_project_fwd_sh<3, *>, k_project_bwd_sh<3, *, *>).
 //
 // The arithmetic follows the reference's order of operations (matrix products accumulated left to right, k
 // ascending, no FMA contraction: the library is built with -ffp-contract=off) so that the integer boxes that come
@@ -25,6 +33,8 @@ constexpr float kShC0 = 0.28209479177387814f;
 constexpr float kShC1 = 0.4886025119029199f;
 constexpr float kShC2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
                             0.5462742152960396f};
+constexpr float kShC3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
+                            -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
 struct Camera {
   float P[12];  // world -> camera [R|t], row major 3x4
@@ -57,6 +67,14 @@ struct Projected {
 };
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// The direction the SH basis is evaluated on.  Camera frame: `view` itself.  World frame: W = P[:, :3] is orthonormal and
+// t = W (m - c), so the unit vector from the camera centre c to the Gaussian is W^T t / |t| = -W^T view.
+template <bool WORLD>
+__device__ __forceinline__ void sh_direction(const float* __restrict__ P, const float* __restrict__ view, float* __restrict__ dir) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) dir[k] = WORLD ? -((P[k] * view[0] + P[4 + k] * view[1]) + P[8 + k] * view[2]) : view[k];
+}
 
 __device__ __forceinline__ void project_one(const Camera& cam, const float* __restrict__ mean, const float* __restrict__ q,
                                             const float* __restrict__ log_scale, i64 i, Projected& o) {
@@ -183,7 +201,9 @@ __device__ __forceinline__ int trunc_i32(float v) { return (int)v; }
 // Per Gaussian, one 64-byte record (what the gather reads back in one piece), the sort key of its depth and the cull flag.
 //   record words: 0-3 box x0 y0 x1 y1 | 4-5 pixel mean | 6-9 Sigma'^-1 | 10 opacity | 11-13 colour | 14 camera depth | 15 unused
 
-__global__ __launch_bounds__(kThreads) void k_project_fwd(
+// MAXDEG: the highest SH degree the instantiation can evaluate (sh_degree <= MAXDEG is the caller's to ensure).
+template <int MAXDEG, bool WORLD>
+__device__ __forceinline__ void project_fwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
     const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp,
@@ -212,9 +232,11 @@ __global__ __launch_bounds__(kThreads) void k_project_fwd(
     row_of[i] = -1;
     // kept depths are positive floats: their bit patterns sort like the values; culled Gaussians sort last
     sort_key[i] = k ? __float_as_int(p.t[2]) : 0x7fffffff;
-    // real spherical harmonics, degree <= 2 (the build's eval_sh; the reference's sh_utility is absent)
+    // real spherical harmonics (the build's eval_sh; the reference's sh_utility is absent)
     const float* sh = tile.sh + threadIdx.x * n_basis * 3;
-    const float x = p.view[0], y = p.view[1], z = p.view[2];
+    float dir[3];
+    sh_direction<WORLD>(cam.P, p.view, dir);
+    const float x = dir[0], y = dir[1], z = dir[2];
     float l[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -228,6 +250,13 @@ __global__ __launch_bounds__(kThreads) void k_project_fwd(
               kShC2[4] * (xx - yy) * sh[24 + ch];
         }
       }
+      if (MAXDEG > 2 && sh_degree > 2) {  // after the degree-2 chain, which stays as it is: zero rows 9..15 add +-0, exactly
+        const float xx = x * x, yy = y * y, zz = z * z;
+        v = ((((((v + kShC3[0] * y * (3.f * xx - yy) * sh[27 + ch]) + kShC3[1] * (x * y * z) * sh[30 + ch]) +
+                kShC3[2] * y * (4.f * zz - xx - yy) * sh[33 + ch]) + kShC3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * sh[36 + ch]) +
+              kShC3[4] * x * (4.f * zz - xx - yy) * sh[39 + ch]) + kShC3[5] * z * (xx - yy) * sh[42 + ch]) +
+            kShC3[6] * x * (xx - 3.f * yy) * sh[45 + ch];
+      }
       l[ch] = v;
     }
     const float alpha = 1.f / (1.f + expf(-opacity[i]));
@@ -237,6 +266,23 @@ __global__ __launch_bounds__(kThreads) void k_project_fwd(
     rec[2] = make_float4(-p.c / p.det, p.a / p.det, alpha, l[0]);
     rec[3] = make_float4(l[1], l[2], p.t[2], 0.f);
   }
+}
+
+#define GCP_PROJECT_FWD_PARAMS                                                                                              \
+  const float *__restrict__ mean, const float *__restrict__ q, const float *__restrict__ log_scale,                        \
+      const float *__restrict__ opacity, const float *__restrict__ color, const float *__restrict__ cam_P,                 \
+      const float *__restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp,          \
+      float4 *__restrict__ record, int *__restrict__ sort_key, uint8_t *__restrict__ keep, int *__restrict__ row_of
+#define GCP_PROJECT_FWD_ARGS \
+  mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, width, height, box_clamp, record, sort_key, keep, row_of
+
+// degree <= 2 on the camera-frame direction: what every call ran before degree 3 and the world frame existed
+__global__ __launch_bounds__(kThreads) void k_project_fwd(GCP_PROJECT_FWD_PARAMS) { project_fwd<2, false>(GCP_PROJECT_FWD_ARGS); }
+
+// <2, true>: degree <= 2, world frame; <3, false> and <3, true>: degree 3
+template <int MAXDEG, bool WORLD>
+__global__ __launch_bounds__(kThreads) void k_project_fwd_sh(GCP_PROJECT_FWD_PARAMS) {
+  project_fwd<MAXDEG, WORLD>(GCP_PROJECT_FWD_ARGS);
 }
 
 // Row r of the depth-ordered list is Gaussian perm[r]: unpack its record into the Function's argument arrays (DEPTH: and its
@@ -288,7 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_project_gather_depth(
 // One thread per Gaussian, in the Gaussians' own order (coalesced parameter reads and gradient writes); the only
 // scattered reads are the 8 upstream gradient words of its row `row_of[i]` in the depth-ordered list.  Culled
 // Gaussians (row -1) get zeros: every gradient row is written, nothing needs clearing first.
-template <bool DEPTH>
+template <int MAXDEG, bool WORLD, bool DEPTH>
 __device__ __forceinline__ void project_bwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
@@ -331,38 +377,64 @@ __device__ __forceinline__ void project_bwd(
     const float al = 1.f / (1.f + expf(-opacity[i]));
     grad_opacity[i] = g_alpha[r] * al * (1.f - al);
 
-    // colour: l_d[ch] = sum_k B_k(view) sh[k][ch]
-    const float x = p.view[0], y = p.view[1], z = p.view[2];
-    float Bk[9] = {kShC0, -kShC1 * y, kShC1 * z, -kShC1 * x, kShC2[0] * x * y, kShC2[1] * y * z,
-                   kShC2[2] * (2.f * z * z - x * x - y * y), kShC2[3] * x * z, kShC2[4] * (x * x - y * y)};
+    // colour: l_d[ch] = sum_k B_k(dir) sh[k][ch]
+    constexpr int NB = (MAXDEG + 1) * (MAXDEG + 1);
+    float dir[3];
+    sh_direction<WORLD>(cam.P, p.view, dir);
+    const float x = dir[0], y = dir[1], z = dir[2];
+    float Bk[NB] = {kShC0, -kShC1 * y, kShC1 * z, -kShC1 * x, kShC2[0] * x * y, kShC2[1] * y * z,
+                    kShC2[2] * (2.f * z * z - x * x - y * y), kShC2[3] * x * z, kShC2[4] * (x * x - y * y)};
+    if (MAXDEG > 2) {
+      const float xx = x * x, yy = y * y, zz = z * z;
+      const float B3[7] = {kShC3[0] * y * (3.f * xx - yy), kShC3[1] * (x * y * z), kShC3[2] * y * (4.f * zz - xx - yy),
+                           kShC3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy), kShC3[4] * x * (4.f * zz - xx - yy),
+                           kShC3[5] * z * (xx - yy), kShC3[6] * x * (xx - 3.f * yy)};
+#pragma unroll
+      for (int k = 9; k < NB; ++k) Bk[k] = B3[k - 9];
+    }
     const int nb = (sh_degree + 1) * (sh_degree + 1);
-    float gv[3] = {0.f, 0.f, 0.f};  // dL/dview
+    float gd[3] = {0.f, 0.f, 0.f};  // dL/ddir
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float g = g_ld[3 * r + ch];
       // this channel's coefficients first: the gradient row goes into the very words they are read from
-      float c[9];
+      float c[NB];
 #pragma unroll
-      for (int k = 0; k < 9; ++k) c[k] = k < nb ? gsh[3 * k + ch] : 0.f;
+      for (int k = 0; k < NB; ++k) c[k] = k < nb ? gsh[3 * k + ch] : 0.f;
 #pragma unroll
-      for (int k = 0; k < 9; ++k)
+      for (int k = 0; k < NB; ++k)
         if (k < n_basis) gsh[3 * k + ch] = k < nb ? g * Bk[k] : 0.f;
-      for (int k = 9; k < n_basis; ++k) gsh[3 * k + ch] = 0.f;
+      for (int k = NB; k < n_basis; ++k) gsh[3 * k + ch] = 0.f;
       if (sh_degree > 0) {
-        gv[0] += g * (-kShC1 * c[3]);
-        gv[1] += g * (-kShC1 * c[1]);
-        gv[2] += g * (kShC1 * c[2]);
+        gd[0] += g * (-kShC1 * c[3]);
+        gd[1] += g * (-kShC1 * c[1]);
+        gd[2] += g * (kShC1 * c[2]);
         if (sh_degree > 1) {
-          gv[0] += g * (kShC2[0] * y * c[4] - 2.f * kShC2[2] * x * c[6] + kShC2[3] * z * c[7] + 2.f * kShC2[4] * x * c[8]);
-          gv[1] += g * (kShC2[0] * x * c[4] + kShC2[1] * z * c[5] - 2.f * kShC2[2] * y * c[6] - 2.f * kShC2[4] * y * c[8]);
-          gv[2] += g * (kShC2[1] * y * c[5] + 4.f * kShC2[2] * z * c[6] + kShC2[3] * x * c[7]);
+          gd[0] += g * (kShC2[0] * y * c[4] - 2.f * kShC2[2] * x * c[6] + kShC2[3] * z * c[7] + 2.f * kShC2[4] * x * c[8]);
+          gd[1] += g * (kShC2[0] * x * c[4] + kShC2[1] * z * c[5] - 2.f * kShC2[2] * y * c[6] - 2.f * kShC2[4] * y * c[8]);
+          gd[2] += g * (kShC2[1] * y * c[5] + 4.f * kShC2[2] * z * c[6] + kShC2[3] * x * c[7]);
         }
       }
+      if (MAXDEG > 2 && sh_degree > 2) {
+        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
+        const float* c3 = c + (MAXDEG > 2 ? 9 : 0);  // rows 9..15
+        gd[0] += g * (6.f * kShC3[0] * xy * c3[0] + kShC3[1] * yz * c3[1] - 2.f * kShC3[2] * xy * c3[2] - 6.f * kShC3[3] * xz * c3[3] +
+                      kShC3[4] * (4.f * zz - 3.f * xx - yy) * c3[4] + 2.f * kShC3[5] * xz * c3[5] + 3.f * kShC3[6] * (xx - yy) * c3[6]);
+        gd[1] += g * (3.f * kShC3[0] * (xx - yy) * c3[0] + kShC3[1] * xz * c3[1] + kShC3[2] * (4.f * zz - xx - 3.f * yy) * c3[2] -
+                      6.f * kShC3[3] * yz * c3[3] - 2.f * kShC3[4] * xy * c3[4] - 2.f * kShC3[5] * yz * c3[5] - 6.f * kShC3[6] * xy * c3[6]);
+        gd[2] += g * (kShC3[1] * xy * c3[1] + 8.f * kShC3[2] * yz * c3[2] + 3.f * kShC3[3] * (2.f * zz - xx - yy) * c3[3] +
+                      8.f * kShC3[4] * xz * c3[4] + kShC3[5] * (xx - yy) * c3[5]);
+      }
     }
+    // world frame: dir = -W^T view  ->  dL/dview = -W dL/ddir
+    float gv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      gv[k] = WORLD ? -((cam.P[4 * k] * gd[0] + cam.P[4 * k + 1] * gd[1]) + cam.P[4 * k + 2] * gd[2]) : gd[k];
     float gt[3];  // dL/dt (camera-space mean)
     {
-      const float dot = gv[0] * x + gv[1] * y + gv[2] * z;
-      const float vv[3] = {x, y, z};
+      const float* vv = p.view;
+      const float dot = gv[0] * vv[0] + gv[1] * vv[1] + gv[2] * vv[2];
 #pragma unroll
       for (int k = 0; k < 3; ++k) gt[k] = -(gv[k] - vv[k] * dot) / p.tlen;
     }
@@ -470,29 +542,60 @@ __device__ __forceinline__ void project_bwd(
   }
 }
 
-__global__ __launch_bounds__(kThreads) void k_project_bwd(
-    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
-    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
-    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
-    const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
-    float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
-    float* __restrict__ grad_opacity, float* __restrict__ grad_color) {
-  project_bwd<false>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv, g_alpha, g_ld, nullptr,
-                     grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color);
+#define GCP_PROJECT_BWD_PARAMS                                                                                              \
+  const float *__restrict__ mean, const float *__restrict__ q, const float *__restrict__ log_scale,                        \
+      const float *__restrict__ opacity, const float *__restrict__ color, const float *__restrict__ cam_P,                 \
+      const float *__restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int *__restrict__ row_of,                  \
+      const float *__restrict__ g_vinv, const float *__restrict__ g_alpha, const float *__restrict__ g_ld
+#define GCP_PROJECT_BWD_GRADS                                                                                               \
+  float *__restrict__ grad_mean, float *__restrict__ grad_q, float *__restrict__ grad_log_scale,                           \
+      float *__restrict__ grad_opacity, float *__restrict__ grad_color
+#define GCP_PROJECT_BWD_ARGS mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv, g_alpha, g_ld
+#define GCP_PROJECT_BWD_GRAD_ARGS grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color
+
+// degree <= 2 on the camera-frame direction, without and with the depth gradient
+__global__ __launch_bounds__(kThreads) void k_project_bwd(GCP_PROJECT_BWD_PARAMS, GCP_PROJECT_BWD_GRADS) {
+  project_bwd<2, false, false>(GCP_PROJECT_BWD_ARGS, nullptr, GCP_PROJECT_BWD_GRAD_ARGS);
 }
 
-__global__ __launch_bounds__(kThreads) void k_project_bwd_depth(
-    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
-    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
-    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
-    const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
-    const float* __restrict__ g_depth, float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
-    float* __restrict__ grad_opacity, float* __restrict__ grad_color) {
-  project_bwd<true>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv, g_alpha, g_ld, g_depth,
-                    grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color);
+__global__ __launch_bounds__(kThreads) void k_project_bwd_depth(GCP_PROJECT_BWD_PARAMS, const float* __restrict__ g_depth,
+                                                                GCP_PROJECT_BWD_GRADS) {
+  project_bwd<2, false, true>(GCP_PROJECT_BWD_ARGS, g_depth, GCP_PROJECT_BWD_GRAD_ARGS);
+}
+
+// <2, true, *>: degree <= 2, world frame; <3, *, *>: degree 3
+template <int MAXDEG, bool WORLD, bool DEPTH>
+__global__ __launch_bounds__(kThreads) void k_project_bwd_sh(GCP_PROJECT_BWD_PARAMS, const float* __restrict__ g_depth,
+                                                             GCP_PROJECT_BWD_GRADS) {
+  project_bwd<MAXDEG, WORLD, DEPTH>(GCP_PROJECT_BWD_ARGS, g_depth, GCP_PROJECT_BWD_GRAD_ARGS);
 }
 
 int grid_for(i64 n) { return (int)((n + kThreads - 1) / kThreads < 65536 ? (n + kThreads - 1) / kThreads : 65536); }
+
+bool sh_arguments_valid(int32_t sh_degree, int32_t n_basis, int32_t sh_frame) {
+  return sh_degree >= 0 && sh_degree <= 3 && n_basis >= (sh_degree + 1) * (sh_degree + 1) && (sh_frame == 0 || sh_frame == 1);
+}
+
+int project_forward_call(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                         const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                         int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float* record,
+                         int32_t* sort_key, uint8_t* keep, int32_t* row_of, void* stream) {
+  if (n_gauss < 0 || n_gauss > 0x7fffffff || !sh_arguments_valid(sh_degree, n_basis, sh_frame) || width < 0 || height < 0)
+    return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss == 0) return GCP_OK;
+  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !record || !sort_key || !keep ||
+      !row_of || ((uintptr_t)record & 15))
+    return GCP_ERR_INVALID_ARGUMENT;
+  const size_t lds_fwd = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
+  if (lds_fwd > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
+  const bool deg3 = sh_degree > 2, world = sh_frame == 1;
+  auto kernel = deg3 ? (world ? k_project_fwd_sh<3, true> : k_project_fwd_sh<3, false>) : (world ? k_project_fwd_sh<2, true> : k_project_fwd);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n_gauss)), dim3(kThreads), lds_fwd, (hipStream_t)stream, mean, quat_xyzw, log_scale,
+                     opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, (int)width, (int)height,
+                     box_clamp, (float4*)record, sort_key, keep, row_of);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
 
 }  // namespace
 
@@ -502,20 +605,16 @@ int gcp_project_forward(const float* mean, const float* quat_xyzw, const float* 
                         const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
                         int32_t n_basis, int32_t width, int32_t height, float box_clamp, float* record, int32_t* sort_key,
                         uint8_t* keep, int32_t* row_of, void* stream) {
-  if (n_gauss < 0 || n_gauss > 0x7fffffff || sh_degree < 0 || sh_degree > 2 || n_basis < (sh_degree + 1) * (sh_degree + 1) ||
-      width < 0 || height < 0)
-    return GCP_ERR_INVALID_ARGUMENT;
-  if (n_gauss == 0) return GCP_OK;
-  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !record || !sort_key || !keep ||
-      !row_of || ((uintptr_t)record & 15))
-    return GCP_ERR_INVALID_ARGUMENT;
-  const size_t lds_fwd = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
-  if (lds_fwd > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
-  hipLaunchKernelGGL(k_project_fwd, dim3(grid_for(n_gauss)), dim3(kThreads), lds_fwd, (hipStream_t)stream, mean, quat_xyzw, log_scale,
-                     opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, (int)width, (int)height,
-                     box_clamp, (float4*)record, sort_key, keep, row_of);
-  GCP_HIP(hipGetLastError());
-  return GCP_OK;
+  return project_forward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, 0, width,
+                              height, box_clamp, record, sort_key, keep, row_of, stream);
+}
+
+int gcp_project_forward_sh(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                           const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                           int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float* record,
+                           int32_t* sort_key, uint8_t* keep, int32_t* row_of, void* stream) {
+  return project_forward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, sh_frame,
+                              width, height, box_clamp, record, sort_key, keep, row_of, stream);
 }
 
 }  // extern "C"
@@ -544,24 +643,35 @@ int project_gather_call(const float* record, const int32_t* perm, int64_t n_kept
 
 int project_backward_call(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
                           const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
-                          int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                          int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                           const float* grad_l_d, const float* grad_depth, bool with_depth, float* grad_mean, float* grad_quat,
                           float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
-  if (n_gauss < 0 || sh_degree < 0 || sh_degree > 2 || n_basis < (sh_degree + 1) * (sh_degree + 1)) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss < 0 || !sh_arguments_valid(sh_degree, n_basis, sh_frame)) return GCP_ERR_INVALID_ARGUMENT;
   if (n_gauss == 0) return GCP_OK;
   if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !row_of || !grad_mean ||
       !grad_quat || !grad_log_scale || !grad_opacity_logit || !grad_sh_coeff)
     return GCP_ERR_INVALID_ARGUMENT;  // the upstream arrays may be NULL when no Gaussian was kept
   const size_t lds = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
   if (lds > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
-  if (with_depth)
-    hipLaunchKernelGGL(k_project_bwd_depth, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
-                       opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
-                       grad_l_d, grad_depth, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
-  else
-    hipLaunchKernelGGL(k_project_bwd, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
-                       opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
-                       grad_l_d, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  const dim3 grid(grid_for(n_gauss)), block(kThreads);
+  const bool deg3 = sh_degree > 2, world = sh_frame == 1;
+  if (!deg3 && !world) {
+    if (with_depth)
+      hipLaunchKernelGGL(k_project_bwd_depth, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff,
+                         cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth,
+                         grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+    else
+      hipLaunchKernelGGL(k_project_bwd, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P,
+                         cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_mean, grad_quat,
+                         grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  } else {
+    auto kernel = deg3 ? (world ? (with_depth ? k_project_bwd_sh<3, true, true> : k_project_bwd_sh<3, true, false>)
+                                : (with_depth ? k_project_bwd_sh<3, false, true> : k_project_bwd_sh<3, false, false>))
+                       : (with_depth ? k_project_bwd_sh<2, true, true> : k_project_bwd_sh<2, true, false>);
+    hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K,
+                       (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth, grad_mean,
+                       grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  }
   GCP_HIP(hipGetLastError());
   return GCP_OK;
 }
@@ -589,7 +699,7 @@ int gcp_project_backward(const float* mean, const float* quat_xyzw, const float*
                          int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                          const float* grad_l_d, float* grad_mean, float* grad_quat, float* grad_log_scale,
                          float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
-  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, row_of,
+  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, 0, row_of,
                                grad_vinv, grad_alpha, grad_l_d, nullptr, false, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit,
                                grad_sh_coeff, stream);
 }
@@ -599,9 +709,19 @@ int gcp_project_backward_depth(const float* mean, const float* quat_xyzw, const 
                                int32_t n_basis, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                                const float* grad_l_d, const float* grad_depth, float* grad_mean, float* grad_quat,
                                float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
-  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, row_of,
+  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, 0, row_of,
                                grad_vinv, grad_alpha, grad_l_d, grad_depth, true, grad_mean, grad_quat, grad_log_scale,
                                grad_opacity_logit, grad_sh_coeff, stream);
+}
+
+int gcp_project_backward_sh(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                            const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                            int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                            const float* grad_l_d, const float* grad_depth, float* grad_mean, float* grad_quat,
+                            float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
+  return project_backward_call(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, sh_frame,
+                               row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth, grad_depth != nullptr, grad_mean, grad_quat,
+                               grad_log_scale, grad_opacity_logit, grad_sh_coeff, stream);
 }
 
 }  // extern "C"

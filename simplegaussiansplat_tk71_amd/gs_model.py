@@ -16,7 +16,10 @@ arguments the reference hands to `custom_autograd_grouped_cumprod.apply`).  Diff
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
   * one Function call per camera, never chunked (nothing of pair-list size exists here; gs_model.py:428);
   * the SH colour stands in for the reference's `sh_utility.eval_sh`, which is not in its checkout
-    (gs_model.py:9,335): real spherical harmonics up to degree 2 in the usual 3DGS convention — parity unpinned;
+    (gs_model.py:9,335): real spherical harmonics up to degree 3 in the usual 3DGS order and sign — parity unpinned.
+    The direction they are evaluated on is, by default, the reference's: -t/|t| in CAMERA coordinates (:335-338), so a
+    Gaussian changes colour when the camera rolls; `sh_frame="world"` uses the world-space unit vector from the camera
+    centre to the Gaussian, the convention of other 3DGS renderers (what a scene saved with `save_ply` needs);
   * tensors live on the parameters' device instead of a hard-coded "cuda";
   * on the GPU the whole per-Gaussian chain is ONE HIP kernel per camera and direction (`gcp_project_forward`,
     `gcp_project_backward`, csrc/gcp_project.hip) instead of ~150 PyTorch kernels: at 10^6 Gaussians the reference's
@@ -31,6 +34,8 @@ import torch
 from . import _lib
 from . import raster as _raster
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
+
+SH_FRAMES = {"camera": 0, "world": 1}
 
 __all__ = [
     "GS_dataset",
@@ -94,11 +99,12 @@ def _box_clamp(width, height, tile_max_width):
 class _ProjectCamera(torch.autograd.Function):
     """One camera of `camera_inputs` on the HIP library (csrc/gcp_project.hip): gcp_project_forward, the library's
     stable radix sort on the depth keys, gcp_project_gather; backward = gcp_project_backward.  with_depth: the camera-space
-    depths too, right after l_d (gcp_project_gather_depth / gcp_project_backward_depth)."""
+    depths too, right after l_d (gcp_project_gather_depth / gcp_project_backward_depth).  `L_max` is the ACTIVE degree, which
+    may be below what `color` stores; `sh_frame` 0 / 1 = camera / world directions (the gcp_project_*_sh entry points)."""
 
     @staticmethod
     def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
-                capture_safe=False, with_depth=False):
+                capture_safe=False, with_depth=False, sh_frame=0):
         dev, n = mean.device, mean.shape[0]
         args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
         for t in args:
@@ -113,9 +119,9 @@ class _ProjectCamera(torch.autograd.Function):
         keep = torch.empty(n, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.gcp_project_forward(*(t.data_ptr() for t in args), n, L_max, color.shape[1], width, height, box_clamp,
-                                               record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream),
-                       "gcp_project_forward")
+            _lib.check(lib.gcp_project_forward_sh(*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height,
+                                                  box_clamp, record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(),
+                                                  stream), "gcp_project_forward")
             # the one device->host read: sizes of the outputs.  capture_safe: none — the list keeps all n Gaussians, the
             # culled ones behind the kept ones with empty boxes (gcp_project_gather with the keep mask)
             m = n if capture_safe else (int(keep.sum()) if n else 0)
@@ -137,7 +143,7 @@ class _ProjectCamera(torch.autograd.Function):
                                                   keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather")
         keep = keep.view(torch.bool)
         ctx.save_for_backward(*args, row_of)
-        ctx.L_max, ctx.with_depth = L_max, with_depth
+        ctx.L_max, ctx.with_depth, ctx.sh_frame = L_max, with_depth, sh_frame
         out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), start, end, mean_xy, boxsize, index, keep)
         ctx.mark_non_differentiable(*out[-6:])
         return out
@@ -148,16 +154,17 @@ class _ProjectCamera(torch.autograd.Function):
         mean, variance_q, variance_scale, opacity, color = args[:5]
         grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
         g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:1 if ctx.with_depth else 0])]
+        g_depth = g[3].data_ptr() if ctx.with_depth else None
         with torch.cuda.device(mean.device):
             stream = torch.cuda.current_stream(mean.device).cuda_stream
-            entry = _lib.load().gcp_project_backward_depth if ctx.with_depth else _lib.load().gcp_project_backward
-            _lib.check(entry(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1], row_of.data_ptr(),
-                             *(t.data_ptr() for t in g), *(t.data_ptr() for t in grads), stream), "gcp_project_backward")
-        return (*grads, None, None, None, None, None, None, None, None)
+            _lib.check(_lib.load().gcp_project_backward_sh(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1],
+                                                           ctx.sh_frame, row_of.data_ptr(), *(t.data_ptr() for t in g[:3]), g_depth,
+                                                           *(t.data_ptr() for t in grads), stream), "gcp_project_backward")
+        return (*grads, None, None, None, None, None, None, None, None, None)
 
 
 def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
-                  with_depth=False):
+                  with_depth=False, sh_frame="camera"):
     """Per camera, the depth-ordered, culled arguments of the Function (reference: gs_model.py:277-425).
 
     mean (N,3), variance_q (N,4 xyzw), variance_scale (N,3 log), opacity (N,1 logit), color (N,(L+1)^2,3),
@@ -176,14 +183,21 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
 
     with_depth=True: every dict also holds "depth", the Gaussians' camera-space depths in list order (the positive depth
     they are sorted by; 0 for the culled entries of a capture-safe list), differentiable w.r.t. `mean` — the `depth`
-    argument of `cuda_kernel.render`."""
+    argument of `cuda_kernel.render`.
+
+    L_max (0..3) is the ACTIVE SH degree: `color` may store more rows than (L_max+1)^2; those are not read and get exact
+    zero gradients.  sh_frame: "camera" (the default, the reference's: the SH basis is evaluated on -t/|t| in camera
+    coordinates) or "world" (on the world-space unit vector from the camera centre to the Gaussian, as other 3DGS
+    renderers do: the colour does not change when the camera rolls)."""
+    if sh_frame not in SH_FRAMES:
+        raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
     width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
     clamp = _box_clamp(width, height, tile_max_width)
     grad_iter = None
     cams = []
     for c in range(P.shape[0]):
         out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
-                                   capture_safe, with_depth)
+                                   capture_safe, with_depth, SH_FRAMES[sh_frame])
         vinv, alpha, l_d = out[:3]
         start, end, mean_xy, boxsize, index, keep = out[-6:]
         grad_iter = keep if grad_iter is None else grad_iter | keep
@@ -267,8 +281,18 @@ class GS_model_with_param(torch.nn.Module):
                  percent_dense=0.01, prunning_min_opacity=0.005, variance_pixel_tile_max_width=0.04,
                  position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
-                 rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False):
+                 rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
+                 active_sh_degree=None):
+        """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
+        the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame: see `camera_inputs`."""
         super().__init__()
+        if not 0 <= L_max <= 3:
+            raise ValueError(f"L_max: 0..3, got {L_max}")
+        if sh_frame not in SH_FRAMES:
+            raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
+        active_sh_degree = L_max if active_sh_degree is None else int(active_sh_degree)
+        if not 0 <= active_sh_degree <= L_max:
+            raise ValueError(f"active_sh_degree: 0..L_max, got {active_sh_degree}")
         self.grad_delta_upper_limit, self.grad_threshold = grad_delta_upper_limit, grad_threshold
         self.percent_dense, self.prunning_min_opacity = percent_dense, prunning_min_opacity
         self.variance_pixel_tile_max_width = math.log(variance_pixel_tile_max_width / (1 - variance_pixel_tile_max_width))
@@ -283,7 +307,7 @@ class GS_model_with_param(torch.nn.Module):
                                                  lr_delay_mult=position_lr_delay_mult, max_steps=position_lr_max_steps)
         self.lr = {"mean": self.mean_lr_setfunc(0), "variance_q": rotation_lr, "variance_scale": scaling_lr,
                    "opacity": opacity_lr, "color": feature_lr}
-        self._L_max = L_max
+        self._L_max, self.sh_frame, self.active_sh_degree = L_max, sh_frame, active_sh_degree
         self.reference_layout = reference_layout
         self.mean_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
         self.mean_grads_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int16)
@@ -308,6 +332,12 @@ class GS_model_with_param(torch.nn.Module):
         self._optimizer.step()
         self._optimizer.zero_grad(set_to_none=True)
         return self
+
+    def oneup_sh_degree(self):
+        """Activate the next SH degree, up to L_max; returns the active degree.  Rows above it keep exact zero gradients,
+        and Adam leaves a row with zero gradient and zero moments where it is: they start training when they are activated."""
+        self.active_sh_degree = min(self.active_sh_degree + 1, self._L_max)
+        return self.active_sh_degree
 
     # ---- camera data parallelism (one process per GPU; the reference is single-GPU) ----------------------------
     def allreduce_grads(self, grad_iter=None, group=None):
@@ -398,9 +428,38 @@ class GS_model_with_param(torch.nn.Module):
         self.changing_optimizer()
 
     # ---- forward (:277-460) ------------------------------------------------------------------------------------
-    def camera_inputs(self, P, K, wh, with_depth=False):
+    def camera_inputs(self, P, K, wh, with_depth=False, capture_safe=False):
         return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
-                             self.variance_pixel_tile_max_width, self._L_max, with_depth=with_depth)
+                             self.variance_pixel_tile_max_width, self.active_sh_degree, capture_safe=capture_safe,
+                             with_depth=with_depth, sh_frame=self.sh_frame)
+
+    # ---- scene files (ply_io) ------------------------------------------------------------------------------------
+    def save_ply(self, path, convention="3dgs"):
+        """The scene as a standard 3DGS .ply (ply_io.save_ply).  Other renderers evaluate the SH basis on world-space
+        directions: a model in the camera frame with an active degree > 0 is saved with a warning."""
+        from . import ply_io
+
+        if self.sh_frame != "world" and self.active_sh_degree > 0:
+            import warnings
+
+            warnings.warn("save_ply: this model evaluates its SH colour on camera-frame directions (sh_frame='camera'); other "
+                          "renderers use world-space directions, so the view dependence of the saved scene will be wrong there")
+        ply_io.save_ply(path, self.mean.data, self.variance_q.data, self.variance_scale.data, self.opacity.data, self.color.data,
+                        convention=convention)
+
+    @classmethod
+    def from_ply(cls, path, device="cpu", convention="3dgs", **model_kwargs):
+        """A model of the scene in `path` (ply_io.load_ply); L_max comes from the file's number of SH coefficients."""
+        from . import ply_io
+
+        mean, variance_q, variance_scale, opacity, color = ply_io.load_ply(path, device=device, convention=convention)
+        L_max = math.isqrt(color.shape[1]) - 1
+        if model_kwargs.setdefault("L_max", L_max) != L_max:
+            raise ValueError(f"{path} holds degree {L_max}, L_max={model_kwargs['L_max']} was asked for")
+        model = cls(mean, variance_q, variance_scale, opacity, **model_kwargs)
+        with torch.no_grad():
+            model.color.copy_(color)
+        return model
 
     def forward(self, P, K, wh, image_sample):
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh)
