@@ -12,6 +12,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
                                                              # degree-3 colour on world-space directions, one degree more
                                                              # every 100 steps, saved as a standard 3DGS .ply
     python examples/train_cameras.py --load-ply scene.ply --sh-frame world      # resume from such a file
+    python examples/train_cameras.py --centres subpixel --dilation 0.3 --clamp-colour
+                                                             # float splat centres at px + 0.5 (their gradient trains the
+                                                             # positions), 0.3 px^2 covariance dilation, colour clamped at 0
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -72,7 +75,7 @@ def load_colmap(root, device):
 def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2, opacity_init=0.1, neighbours=3,
           densify_from_iter=500, densify_until_iter=15000, densification_interval=100, opacity_reset_interval=3000,
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
-          sh_frame="camera", sh_every=0, save_ply=None, load_ply=None):
+          sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -80,7 +83,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `target_alpha` (B, 1, H, W) is given, the targets composited over it too.
     `sh_degree` (0..3) and `sh_frame` ("camera" / "world"): the appearance model (gs_model.camera_inputs); `sh_every` N > 0:
     start at degree 0 and activate one more every N iterations.  `load_ply`: start from that scene file instead of `start`
-    (its degree replaces `sh_degree`); `save_ply`: write the trained scene there (rank 0)."""
+    (its degree replaces `sh_degree`); `save_ply`: write the trained scene there (rank 0).
+    `centres`, `dilation`, `clamp_colour`: the projection's `centres`, `cov_dilation`, `clamp_colour` (gs_model.camera_inputs)."""
     if isinstance(background, str) and background != "random":
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
@@ -90,7 +94,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     q[:, 3] = 1  # identity rotation, (x, y, z, w) (gs_control.py:113-114)
     scale = torch.log(gm.mean_neighbour_distance(neighbours, start))
     opacity = torch.full((n, 1), math.log(opacity_init / (1 - opacity_init)), device=dev)
-    sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None}
+    sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None, "centres": centres, "cov_dilation": dilation,
+          "clamp_colour": clamp_colour}
     if load_ply is not None:
         model = gm.GS_model_with_param.from_ply(load_ply, dev, **sh)
     else:
@@ -169,6 +174,11 @@ if __name__ == "__main__":
     ap.add_argument("--sh-every", type=int, default=0, metavar="N", help="start at degree 0, one degree more every N iterations (0: off)")
     ap.add_argument("--save-ply", default=None, metavar="PATH", help="write the trained scene as a standard 3DGS .ply")
     ap.add_argument("--load-ply", default=None, metavar="PATH", help="start from a 3DGS .ply instead of the point cloud")
+    ap.add_argument("--centres", choices=("pixel", "subpixel"), default="pixel",
+                    help="subpixel = float splat centres at px + 0.5, trained by their own gradient; pixel = truncated (the reference's)")
+    ap.add_argument("--dilation", type=float, default=None, metavar="F",
+                    help="added to the diagonal of the pixel covariance (0.3: other 3DGS renderers'; default 1e-6)")
+    ap.add_argument("--clamp-colour", action="store_true", help="clamp the SH colour at 0")
     a = ap.parse_args()
     background = a.background if a.background in (None, "random") else tuple(float(v) for v in a.background.split(","))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -188,7 +198,8 @@ if __name__ == "__main__":
         start, P, K, wh, targets = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device)
     _, losses = train(start, P, K, wh, targets, iterations=a.iterations, densify_from_iter=a.densify_from, rank=rank, world=world,
                       log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas, sh_degree=a.sh_degree,
-                      sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply)
+                      sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply, centres=a.centres,
+                      dilation=a.dilation, clamp_colour=a.clamp_colour)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

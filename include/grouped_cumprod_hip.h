@@ -576,6 +576,49 @@ int gcp_project_backward_sh(const float* mean, const float* quat_xyzw, const flo
                             float* grad_mean, float* grad_quat, float* grad_log_scale, float* grad_opacity_logit,
                             float* grad_sh_coeff, void* stream);
 
+/* ---- the projection with float centres, covariance dilation and colour clamp (gcp_splat.hip) ----------
+ * The chain of gcp_project_forward_sh / gcp_project_gather[_depth] / gcp_project_backward_sh with the three conventions of
+ * other 3DGS renderers, each chosen by an argument and each with its exact gradient:
+ *   cov_eps (>= 0, finite): added to the diagonal of the pixel covariance in place of 1e-6 — J W S W^T J^T + cov_eps I;
+ *     0.3 is the usual screen-space dilation, 1e-6 the reference's.  det = a d - b c + 1e-6 stays; the 3-sigma half extents
+ *     come from the dilated covariance.
+ *   mean_offset (finite): the pixel centre is kept as two FLOATS, c = clamp(p, +-(2^31 - 1) / 1000) + mean_offset, where
+ *     gcp_project_forward truncates p to integers.  Half-pixel convention: the model crops [1:, 1:] of the (H+1) x (W+1)
+ *     frame, so pixel i of the cropped image is frame pixel i + 1, and in the COLMAP / 3DGS convention that pixel's centre
+ *     lies at i + 0.5 in the coordinates of K.  With mean_offset = 0.5 the blend evaluates dx = (i + 1) - (px + 0.5) =
+ *     (i + 0.5) - px: what those renderers evaluate.  0 keeps the reference's coordinates.
+ *     The box goes around the float centre: with h = min(half extent, box_clamp), columns (int)ceil(cx - h) ..
+ *     (int)floor(cx + h) and rows likewise (the floats clamped to +-(2^31 - 1) / 1000 before conversion): every pixel within
+ *     the clamped 3-sigma extent and no other.  A Gaussian is kept when its depth is > 0, the box is not empty (x1 >= x0,
+ *     y1 >= y0) and x0 < width, x1 > 0, y0 < height, y1 > 0; the stored box is clamped to [0, width] x [0, height].
+ *   clamp_colour (0 or 1): 1 = every channel of the SH colour is max(sum, 0); a channel whose sum is < 0 passes no gradient
+ *     to the coefficients or the direction, a sum of exactly 0 does.
+ * gcp_splat_forward writes record / sort_key / keep / row_of as gcp_project_forward_sh does (record words 4-5: the float
+ * centre).  gcp_splat_gather: as gcp_project_gather, with mean_xy float[n_kept][2] (8-byte aligned, finite for every entry)
+ * and `depth` optional — NULL, or float[n_kept] as gcp_project_gather_depth fills it; `keep` selects the capture-safe form
+ * as there.  gcp_splat_backward: as gcp_project_backward_sh (grad_depth may be NULL) plus grad_mean_xy, NULL or
+ * float[n_kept][2] in list order: dL/dc, chained through px = ph0 / pz, py = ph1 / pz, ph = K t (the full K, skew
+ * included), pz = max(ph2, 1e-2) — dph0 = gx / pz, dph1 = gy / pz, dph2 = -(gx ph0 + gy ph1) / pz^2 where ph2 > 1e-2, else
+ * 0 — into the camera-space gradient K^T dph that reaches `mean` through R; zero where the centre was clamped.
+ * Every entry point returns GCP_ERR_INVALID_ARGUMENT, before any HIP call, for sh_degree / n_basis / sh_frame out of range
+ * (as gcp_project_forward_sh), cov_eps negative or not finite, mean_offset not finite, clamp_colour outside {0, 1}, a NULL
+ * array with Gaussians to process, or a misaligned record / vinv / mean_xy; n_gauss == 0 (n_kept == 0) is a no-op after
+ * the checks of the scalar arguments. */
+int gcp_splat_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                      const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                      int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
+                      float mean_offset, int32_t clamp_colour, float* record, int32_t* sort_key, uint8_t* keep, int32_t* row_of,
+                      void* stream);
+int gcp_splat_gather(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy, float* mean_xy,
+                     int64_t* boxsize, float* vinv, float* alpha, float* l_d, float* depth /* may be NULL */, int64_t* index,
+                     int32_t* row_of, const uint8_t* keep /* may be NULL */, void* stream);
+int gcp_splat_backward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                       const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                       int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                       const float* grad_l_d, const float* grad_depth /* may be NULL */, float cov_eps, int32_t clamp_colour,
+                       const float* grad_mean_xy /* may be NULL */, float* grad_mean, float* grad_quat, float* grad_log_scale,
+                       float* grad_opacity_logit, float* grad_sh_coeff, void* stream);
+
 /* ---- the caller's training loss, fused ---------------------------------------------------
  * (1 - lambda) * mean|a - b| + lambda * (1 - mean SSIM(a, b)) of gs_control.py:180-182 (kornia.metrics.ssim with an
  * 11-tap Gaussian window and reflect padding), over `planes` = batch * channels planes of height x width floats.

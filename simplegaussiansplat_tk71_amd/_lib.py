@@ -117,6 +117,11 @@ SIGNATURES = {
     # the same with the SH direction's frame chosen (0 camera, 1 world); the backward's grad_depth may be NULL
     "gcp_project_forward_sh": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, ctypes.c_float] + [_c_void_p] * 5),
     "gcp_project_backward_sh": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 11),
+    # float centres, covariance dilation, colour clamp (gcp_splat.hip): cov_eps, mean_offset, clamp_colour after box_clamp;
+    # the gather's depth and keep may be NULL; the backward takes cov_eps, clamp_colour and grad_mean_xy (may be NULL) before the outputs
+    "gcp_splat_forward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 3 + [_i32] + [_c_void_p] * 5),
+    "gcp_splat_gather": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
+    "gcp_splat_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5 + [ctypes.c_float, _i32] + [_c_void_p] * 7),
 }
 
 ABI_VERSION = 4

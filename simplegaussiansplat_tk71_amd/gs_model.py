@@ -28,6 +28,7 @@ arguments the reference hands to `custom_autograd_grouped_cumprod.apply`).  Diff
     CPU path (CPU tensors raise).
 """
 import math
+import numbers
 
 import torch
 
@@ -36,6 +37,19 @@ from . import raster as _raster
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 
 SH_FRAMES = {"camera": 0, "world": 1}
+CENTRES = ("pixel", "subpixel")
+
+
+def _splat_options(centres, cov_dilation, clamp_colour):
+    """Validated (centres, cov_eps, clamp_colour) of `camera_inputs`; ValueError before anything touches the GPU."""
+    if centres not in CENTRES:
+        raise ValueError(f"centres: 'pixel' or 'subpixel', got {centres!r}")
+    cov_eps = 1e-6 if cov_dilation is None else cov_dilation
+    if isinstance(cov_eps, bool) or not isinstance(cov_eps, numbers.Real) or not (math.isfinite(cov_eps) and cov_eps >= 0):
+        raise ValueError(f"cov_dilation: None or a finite number >= 0, got {cov_dilation!r}")
+    if not isinstance(clamp_colour, bool):
+        raise ValueError(f"clamp_colour: True or False, got {clamp_colour!r}")
+    return centres, float(cov_eps), clamp_colour
 
 __all__ = [
     "GS_dataset",
@@ -163,8 +177,71 @@ class _ProjectCamera(torch.autograd.Function):
         return (*grads, None, None, None, None, None, None, None, None, None)
 
 
+class _SplatCamera(torch.autograd.Function):
+    """`_ProjectCamera` on the kernels of csrc/gcp_splat.hip (gcp_splat_forward, the same sort, gcp_splat_gather;
+    backward = gcp_splat_backward): `cov_eps` on the diagonal of the pixel covariance, the SH colour clamped at 0
+    (`clamp_colour`), and — `subpixel` — the pixel centre kept as float32 (m, 2) at px + 0.5, differentiable: its gradient is
+    handed to the backward as grad_mean_xy.  Not `subpixel`: the centre is truncated as `_ProjectCamera` truncates it and
+    returned as int32 without a gradient (the box still goes around the untruncated centre, by the rule of the float one)."""
+
+    @staticmethod
+    def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
+                capture_safe, with_depth, sh_frame, subpixel, cov_eps, clamp_colour):
+        dev, n = mean.device, mean.shape[0]
+        args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
+        for t in args:
+            if t.dtype != torch.float32 or t.device != dev:
+                raise RuntimeError("projection expects float32 tensors on one device")
+        if not mean.is_cuda:
+            raise RuntimeError("the fused projection is a HIP kernel: tensors must live on the GPU (no CPU path)")
+        lib = _lib.load()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
+        record, sort_key, row_of = f32(n, 16), i32(n), i32(n)
+        keep = torch.empty(n, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gcp_splat_forward(*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height,
+                                             box_clamp, cov_eps, 0.5 if subpixel else 0.0, int(clamp_colour), record.data_ptr(),
+                                             sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream), "gcp_splat_forward")
+            m = n if capture_safe else (int(keep.sum()) if n else 0)  # as _ProjectCamera: the one device->host read
+            perm = _raster.stable_sort_keys(sort_key, key_bits=31)[1] if n else sort_key
+            start, end, mean_xy, boxsize = i32(m, 2), i32(m, 2), f32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
+            vinv, alpha, l_d, index = f32(m, 2, 2), f32(m, 1), f32(m, 3), torch.empty(m, dtype=torch.int64, device=dev)
+            depth = f32(m) if with_depth else None
+            _lib.check(lib.gcp_splat_gather(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
+                                            mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
+                                            l_d.data_ptr(), depth.data_ptr() if with_depth else None, index.data_ptr(),
+                                            row_of.data_ptr(), keep.data_ptr() if capture_safe else None, stream), "gcp_splat_gather")
+        if not subpixel:
+            mean_xy = mean_xy.to(torch.int32)  # towards zero, as the kernels of gcp_project.hip convert
+        keep = keep.view(torch.bool)
+        ctx.save_for_backward(*args, row_of)
+        ctx.L_max, ctx.with_depth, ctx.sh_frame = L_max, with_depth, sh_frame
+        ctx.subpixel, ctx.cov_eps, ctx.clamp_colour = subpixel, cov_eps, clamp_colour
+        out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), mean_xy, start, end, boxsize, index, keep)
+        ctx.mark_non_differentiable(*out[-(5 if subpixel else 6):])
+        return out
+
+    @staticmethod
+    def backward(ctx, g_vinv, g_alpha, g_ld, *rest):
+        *args, row_of = ctx.saved_tensors
+        mean, variance_q, variance_scale, opacity, color = args[:5]
+        grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
+        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:int(ctx.with_depth) + int(ctx.subpixel)])]
+        g_depth = g[3].data_ptr() if ctx.with_depth else None
+        g_mean_xy = g[-1].data_ptr() if ctx.subpixel else None
+        with torch.cuda.device(mean.device):
+            stream = torch.cuda.current_stream(mean.device).cuda_stream
+            _lib.check(_lib.load().gcp_splat_backward(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1],
+                                                      ctx.sh_frame, row_of.data_ptr(), *(t.data_ptr() for t in g[:3]), g_depth,
+                                                      ctx.cov_eps, int(ctx.clamp_colour), g_mean_xy, *(t.data_ptr() for t in grads),
+                                                      stream), "gcp_splat_backward")
+        return (*grads, *[None] * 12)
+
+
 def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
-                  with_depth=False, sh_frame="camera"):
+                  with_depth=False, sh_frame="camera", centres="pixel", cov_dilation=None, clamp_colour=False):
     """Per camera, the depth-ordered, culled arguments of the Function (reference: gs_model.py:277-425).
 
     mean (N,3), variance_q (N,4 xyzw), variance_scale (N,3 log), opacity (N,1 logit), color (N,(L+1)^2,3),
@@ -188,18 +265,35 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
     L_max (0..3) is the ACTIVE SH degree: `color` may store more rows than (L_max+1)^2; those are not read and get exact
     zero gradients.  sh_frame: "camera" (the default, the reference's: the SH basis is evaluated on -t/|t| in camera
     coordinates) or "world" (on the world-space unit vector from the camera centre to the Gaussian, as other 3DGS
-    renderers do: the colour does not change when the camera rolls)."""
+    renderers do: the colour does not change when the camera rolls).
+
+    Three more conventions of other 3DGS renderers, opt-in (csrc/gcp_splat.hip; with the defaults nothing below runs):
+    centres="subpixel": "mean" is float32 (m, 2) and differentiable — the projected centre px + 0.5 instead of trunc(px), so
+    that the blend's gradient w.r.t. the centre reaches `mean` (with "pixel" a Gaussian's position is trained only through
+    the Jacobian, the view direction and the depth).  The 0.5: pixel i of the cropped image is frame pixel i + 1 and its
+    centre lies at i + 0.5 in the coordinates of K (COLMAP / 3DGS), so dx = (i + 1) - (px + 0.5) = (i + 0.5) - px.  The box
+    is ceil(c - h) .. floor(c + h) around the float centre c, h = the clamped 3-sigma half extent.
+    cov_dilation=F (finite, >= 0; None = 1e-6, the reference's): F is added to the diagonal of the pixel covariance (0.3: the
+    usual screen-space dilation).  clamp_colour=True: l_d = max(SH sum, 0) per channel, no gradient through a clamped channel.
+    centres="pixel" with a dilation or the clamp: "mean" stays int32, truncated as by default, without a gradient."""
     if sh_frame not in SH_FRAMES:
         raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
+    centres, cov_eps, clamp_colour = _splat_options(centres, cov_dilation, clamp_colour)
+    splat = centres != "pixel" or cov_dilation is not None or clamp_colour
     width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
     clamp = _box_clamp(width, height, tile_max_width)
     grad_iter = None
     cams = []
     for c in range(P.shape[0]):
-        out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
-                                   capture_safe, with_depth, SH_FRAMES[sh_frame])
+        if splat:
+            out = _SplatCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
+                                     capture_safe, with_depth, SH_FRAMES[sh_frame], centres == "subpixel", cov_eps, clamp_colour)
+            mean_xy, start, end, boxsize, index, keep = out[-6:]
+        else:
+            out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
+                                       capture_safe, with_depth, SH_FRAMES[sh_frame])
+            start, end, mean_xy, boxsize, index, keep = out[-6:]
         vinv, alpha, l_d = out[:3]
-        start, end, mean_xy, boxsize, index, keep = out[-6:]
         grad_iter = keep if grad_iter is None else grad_iter | keep
         cam = None if index.numel() == 0 else {
             "boxsize": boxsize, "startpoint": start, "endpoint": end, "mean": mean_xy, "variance_inverse": vinv,
@@ -282,9 +376,10 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
-                 active_sh_degree=None):
+                 active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
-        the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame: see `camera_inputs`."""
+        the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
+        clamp_colour: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them."""
         super().__init__()
         if not 0 <= L_max <= 3:
             raise ValueError(f"L_max: 0..3, got {L_max}")
@@ -307,7 +402,9 @@ class GS_model_with_param(torch.nn.Module):
                                                  lr_delay_mult=position_lr_delay_mult, max_steps=position_lr_max_steps)
         self.lr = {"mean": self.mean_lr_setfunc(0), "variance_q": rotation_lr, "variance_scale": scaling_lr,
                    "opacity": opacity_lr, "color": feature_lr}
+        _splat_options(centres, cov_dilation, clamp_colour)
         self._L_max, self.sh_frame, self.active_sh_degree = L_max, sh_frame, active_sh_degree
+        self.centres, self.cov_dilation, self.clamp_colour = centres, cov_dilation, clamp_colour
         self.reference_layout = reference_layout
         self.mean_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
         self.mean_grads_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int16)
@@ -431,7 +528,8 @@ class GS_model_with_param(torch.nn.Module):
     def camera_inputs(self, P, K, wh, with_depth=False, capture_safe=False):
         return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
                              self.variance_pixel_tile_max_width, self.active_sh_degree, capture_safe=capture_safe,
-                             with_depth=with_depth, sh_frame=self.sh_frame)
+                             with_depth=with_depth, sh_frame=self.sh_frame, centres=self.centres, cov_dilation=self.cov_dilation,
+                             clamp_colour=self.clamp_colour)
 
     # ---- scene files (ply_io) ------------------------------------------------------------------------------------
     def save_ply(self, path, convention="3dgs"):
