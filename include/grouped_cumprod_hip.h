@@ -523,6 +523,10 @@ int gcp_pixel_lists_fill(const int32_t* start_xy, const int32_t* end_xy, int64_t
  * sign, sh_degree 0..3, coefficients [n_basis][3] per Gaussian with n_basis >= (sh_degree + 1)^2: rows above the active
  * degree are stored, not read, and get zero gradients), sigmoid opacity, the cull test and the clamped integer box.
  *   cam_P float[12] = [R|t] row major, cam_K float[9] row major, both in device memory;
+ *   mean, quat_xyzw, log_scale, opacity_logit and sh_coeff need only the 4-byte
+ *   alignment of a float — views at any element offset into a larger buffer are fine; an array that happens to be 16-byte
+ *   aligned is read with wider loads, with the same result bit for bit.  This holds for every gcp_project_* and gcp_splat_*
+ *   entry point; the arrays that do need more (record, vinv, start_xy, end_xy, mean_xy) say so below;
  *   box_clamp = the float the 3-sigma half extents are clamped to before truncation (gs_model.py:364-365).
  * gcp_project_forward writes, in the Gaussians' own order: record float[n_gauss][16] (16-byte aligned; opaque, read
  * back by gcp_project_gather), sort_key int32 (bit pattern of the positive camera depth, 0x7fffffff for culled

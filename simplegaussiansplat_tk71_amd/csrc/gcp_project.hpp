@@ -148,11 +148,14 @@ __device__ __forceinline__ ParamTile param_tile(float* base, int n_basis) {
 }
 
 __device__ __forceinline__ void copy_rows(float* __restrict__ dst, const float* __restrict__ src, i64 first_word, int words) {
-  // first_word is a multiple of 4 (256 rows per block), so the run starts 16-byte aligned
+  // first_word is a multiple of 4 (256 rows per block): the run starts 16-byte aligned exactly when the array does.  The
+  // caller's arrays need only 4-byte alignment (a view into a larger buffer); the test is the same for the whole block.
+  // Unaligned: no 16-byte load is issued, the word loop below copies the whole run.
+  const int wide = (reinterpret_cast<uintptr_t>(src + first_word) & 15) == 0 ? (words & ~3) : 0;
   const float4* s4 = reinterpret_cast<const float4*>(src + first_word);
   float4* d4 = reinterpret_cast<float4*>(dst);
-  for (int j = threadIdx.x; j < (words >> 2); j += kThreads) d4[j] = s4[j];
-  for (int j = (words & ~3) + threadIdx.x; j < words; j += kThreads) dst[j] = src[first_word + j];
+  for (int j = threadIdx.x; j < (wide >> 2); j += kThreads) d4[j] = s4[j];
+  for (int j = wide + threadIdx.x; j < words; j += kThreads) dst[j] = src[first_word + j];
 }
 
 __device__ __forceinline__ void load_param_tile(const ParamTile& t, const float* mean, const float* q, const float* log_scale,
@@ -326,7 +329,7 @@ __device__ __forceinline__ void project_bwd(
     // Sigma'^-1 = adj(A) / det  ->  dL/dA
     const float g00 = g_vinv[4 * r], g01 = g_vinv[4 * r + 1], g10 = g_vinv[4 * r + 2], g11 = g_vinv[4 * r + 3];
     const float sdot = ((g00 * p.d - g01 * p.b) - g10 * p.c) + g11 * p.a;
-    const float gdet = -sdot / (p.det * p.det);
+    const float gdet = -(sdot / p.det) / p.det;  // not sdot / det^2: a clamped covariance entry takes det past sqrt(FLT_MAX)
     const float lim = 3.4028234663852886e+38f / 1000.f;
     float D[4] = {g11 / p.det + gdet * p.d, -g01 / p.det - gdet * p.c, -g10 / p.det - gdet * p.b, g00 / p.det + gdet * p.a};
 #pragma unroll

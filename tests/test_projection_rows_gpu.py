@@ -1,0 +1,428 @@
+"""The per-Gaussian projection chain (csrc/gcp_project.hpp: project_one, project_bwd, copy_rows, box_halfsize, sh_colour, as
+csrc/gcp_project.hip and csrc/gcp_splat.hip instantiate it) against the float64 formulation, ROW BY ROW and ONE UPSTREAM AT
+A TIME.
+
+Reference: `tests.test_splat_gpu.formulation` in float64 on the CPU, its lists and integer boxes held fixed at the kernel's
+own (`fixed=`), so that only floats are differentiated.  The same function in float32 on the CPU with the same lists is the
+"float32 formulation": it measures what float32 can deliver on each row.
+
+The row rule, for Gaussian i with `want` the float64 row, `got` the kernel's and `f32` the float32 formulation's:
+
+    |got_i - want_i|_inf  <=  2e-4 |want_i|_inf  +  4 |f32_i - want_i|_inf
+
+2e-4 is the project's rtol for projection outputs, applied per row instead of per tensor; the second term is measured at run
+time and gives an ill-conditioned or analytically zero row what float32 itself needs there; 4 is the margin
+tests/test_splat_gpu.py uses for "the kernel's association differs from torch's".  A row (or an entry) that is exactly zero
+in both precisions of the formulation — a culled Gaussian, a clamped colour channel, a parameter the upstream has no path
+to — must be exactly zero in the kernel's gradient: a zero upstream gradient times finite factors.
+The median check (gradients only): per configuration, path and parameter, the median over live rows of |got_i - want_i|_inf / |want_i|_inf is
+at most 4 x the same median of the float32 formulation (a small systematic error that 2e-4 would let through).
+The condition on the inputs: the float32 formulation's own largest row-relative error stays below 1e-3 for every world, path
+and parameter (tests/test_projection_rows.py asserts the same without a GPU).  The hand-built edge scene is not a world in
+that sense: two of its rows cannot meet the condition (`edge_scene`: the needle in gcp_project, the covariance clamp); they are
+held to the same row rule, whose measured term then carries them.
+
+Not covered, on purpose: the `fabsf(p.px) <= ilim` branch of the centre gradient.  A centre is clamped 2 x 10^6 pixels out;
+its box (at most 10 sqrt(W H) wide) then misses any image of a testable size, the Gaussian is culled and the branch is never
+reached by a kept one.
+
+Every printed line "ROWS ..." is one line of profiles/r11_projection_rows.md."""
+import pytest
+import torch
+
+from simplegaussiansplat_tk71_amd import gs_model as gm
+from simplegaussiansplat_tk71_amd.synthetic import ring_cameras
+from tests.test_sh3_gpu import NAMES, TILE_LOGIT, random_world, torch_sh
+from tests.test_splat_gpu import formulation
+
+pytestmark = pytest.mark.gpu
+
+RTOL, MARGIN, CAP = 2e-4, 4.0, 1e-3
+ALL_SPLAT = {"centres": "subpixel", "cov_dilation": 0.3, "clamp_colour": True}
+# (kernels, options of gm.camera_inputs, active SH degree, stored colour rows, frame, with_depth)
+CONFIGS = {"project-deg2of9-camera": ("project", {}, 2, 9, "camera", False),
+           "project-deg3of16-world-depth": ("project", {}, 3, 16, "world", True),
+           "project-deg0of16-camera-depth": ("project", {}, 0, 16, "camera", True),
+           "splat-subpixel-deg2of9-camera": ("splat", {"centres": "subpixel"}, 2, 9, "camera", False),
+           "splat-all-deg3of16-world-depth": ("splat", ALL_SPLAT, 3, 16, "world", True),
+           "splat-pixel-dilated-clamped-deg1of4-world": ("splat", {"centres": "pixel", "cov_dilation": 0.3, "clamp_colour": True},
+                                                         1, 4, "world", False)}
+# one full 256-row block + a 3-row block (tail words 9, 12, 9 and 9 n_basis: two float4 and one scalar word for mean and
+# log scale) | five blocks + 11 rows, two cameras
+SHAPES = [(259, 1, 40, 30), (1291, 2, 64, 48)]
+EDGE_CONFIGS = {"project": ("project", {}, 3, 16, "world", True), "splat": ("splat", ALL_SPLAT, 3, 16, "world", True)}
+SIZES = (1, 2, 3, 5, 255, 256, 257)
+BASES = (1, 4, 9, 16)
+BIG = SHAPES[0][0]
+
+
+def shape_id(shape):
+    return "x".join(map(str, shape))
+
+
+_WORLDS = {}
+
+
+def world(shape, n_basis):
+    """tests.test_sh3_gpu.random_world on the CPU, one per (shape, stored colour rows), shared and never written to."""
+    if (shape, n_basis) not in _WORLDS:
+        n, n_cam, width, height = shape
+        _WORLDS[shape, n_basis] = random_world(n, n_cam, width, height, 7 + n, "cpu", n_basis=n_basis)
+    return _WORLDS[shape, n_basis]
+
+
+def paths_of(config):
+    _, options, _, _, _, with_depth = config
+    return (("variance_inverse", "opacity", "l_d") + (("depth",) if with_depth else ())
+            + (("mean",) if options.get("centres") == "subpixel" else ()))
+
+
+def upstreams(w, config, seed=1):
+    """Per path, per camera, a random gradient PER GAUSSIAN (float32, CPU): row r of a list gets the one of Gaussian index[r]."""
+    n, n_cam = w["mean"].shape[0], w["P"].shape[0]
+    gen = torch.Generator().manual_seed(seed)
+    tails = {"variance_inverse": (2, 2), "opacity": (1,), "l_d": (3,), "depth": (), "mean": (2,)}
+    return {k: torch.randn((n_cam, n, *tails[k]), generator=gen) for k in tails}
+
+
+def run_formulation(w, config, dtype, fixed=None, sh=None):
+    """The formulation of one configuration on the CPU in `dtype` -> (leaves, cams)."""
+    family, options, degree, _, frame, _ = config
+    centres = "project" if family == "project" else options.get("centres", "pixel")
+    leaves = {k: w[k].detach().cpu().to(dtype).requires_grad_(True) for k in NAMES}
+    P = w["P"].cpu().to(dtype)
+    cams, _ = formulation(*(leaves[k] for k in NAMES), P, w["K"].cpu().to(dtype), w["wh"].cpu(), TILE_LOGIT, degree,
+                          torch_sh(frame, P) if sh is None else sh(frame, P), cov_eps=options.get("cov_dilation", 1e-6),
+                          clamp_colour=options.get("clamp_colour", False), fixed=fixed, centres=centres)
+    return leaves, cams
+
+
+def run_kernels(w, config, device):
+    """gm.camera_inputs of one configuration on the GPU -> (leaves, cams, grad_iter)."""
+    _, options, degree, _, frame, with_depth = config
+    leaves = {k: w[k].to(device).clone().requires_grad_(True) for k in NAMES}
+    cams, grad_iter, _ = gm.camera_inputs(*(leaves[k] for k in NAMES), w["P"].to(device), w["K"].to(device), w["wh"].to(device), TILE_LOGIT,
+                                          L_max=degree, sh_frame=frame, with_depth=with_depth, **options)
+    assert all(cam is not None for cam in cams)
+    return leaves, cams, grad_iter
+
+
+def lists_of(cams):
+    """What `fixed=` takes: the lists and integer boxes of a run."""
+    return [(cam["index"].cpu(), cam["startpoint"].cpu(), cam["endpoint"].cpu()) for cam in cams]
+
+
+def path_gradients(leaves, cams, ups, paths):
+    """{path: {parameter: (N, words) float64 CPU}}: the gradients of sum_cameras <cam[path], upstream> for one path at a time."""
+    out = {}
+    for path in paths:
+        loss = 0
+        for c, cam in enumerate(cams):
+            g = ups[path][c].to(cam[path].device, cam[path].dtype)[cam["index"]]
+            loss = loss + (cam[path] * g).sum()
+        grads = torch.autograd.grad(loss, [leaves[k] for k in NAMES], retain_graph=True, allow_unused=True)
+        out[path] = {k: (torch.zeros_like(leaves[k]) if g is None else g).detach().cpu().double().reshape(leaves[k].shape[0], -1)
+                     for k, g in zip(NAMES, grads)}
+    return out
+
+
+def row_norm(x):
+    return x.reshape(x.shape[0], -1).abs().amax(dim=1)
+
+
+def _median_max(v):
+    return (float(v.median()), float(v.max())) if v.numel() else (0.0, 0.0)
+
+
+def formulation_error(want, f32):
+    """(live rows, row-relative error of the float32 formulation on them)."""
+    scale = row_norm(want)
+    live = scale > 0
+    return live, row_norm(f32 - want)[live] / scale[live]
+
+
+def check_rows(label, got, want, f32, failures, median=True, who="kernel", cap=True):
+    """The row rule, the exact zeros, the median check and the cap on the inputs for one (rows, words) array; prints the line
+    of the note, appends what fails to `failures`."""
+    got, want, f32 = (t.detach().cpu().double().reshape(want.shape[0], -1) for t in (got, want, f32))
+    err, scale, need = row_norm(got - want), row_norm(want), row_norm(f32 - want)
+    bad = ~(err <= RTOL * scale + MARGIN * need)  # a NaN is bad
+    live, rel_f32 = formulation_error(want, f32)
+    rel = err[live] / scale[live]
+    stats = [*_median_max(rel_f32), *_median_max(rel)]
+    worst = int(torch.nonzero(live).flatten()[rel_f32.argmax()]) if rel_f32.numel() else -1
+    print(f"ROWS {label}: rows {int(live.sum())} | float32 formulation median {stats[0]:.2e} max {stats[1]:.2e} (row {worst}) | "
+          f"{who} median {stats[2]:.2e} max {stats[3]:.2e} | outside the row rule {int(bad.sum())}")
+    if bad.any():
+        i = int(torch.nonzero(bad)[0])
+        failures.append(f"{label}: {int(bad.sum())} rows outside the rule, first {i}: got {got[i].tolist()} want {want[i].tolist()} "
+                        f"f32 {f32[i].tolist()}")
+    zero = (want == 0) & (f32 == 0)
+    if bool((got[zero] != 0).any()):
+        failures.append(f"{label}: {int((got[zero] != 0).sum())} entries not exactly zero where both formulations are")
+    if cap and not stats[1] < CAP:
+        failures.append(f"{label}: the float32 formulation itself is {stats[1]:.2e} off on a row (the inputs' cap is {CAP})")
+    if median and rel.numel() and not stats[2] <= MARGIN * stats[0]:
+        failures.append(f"{label}: median row-relative error {stats[2]:.2e} > {MARGIN} x {stats[0]:.2e}")
+
+
+def check_case(tag, w, config, kernel, failures, median=True, who="kernel", cap=True):
+    """kernel = (leaves, cams) of the code under test.  Everything of one configuration on one world under the row rule."""
+    paths, ups = paths_of(config), upstreams(w, config)
+    fixed = lists_of(kernel[1])
+    l64, c64 = run_formulation(w, config, torch.float64, fixed)
+    l32, c32 = run_formulation(w, config, torch.float32, fixed)
+    for c, (got, want, f32) in enumerate(zip(kernel[1], c64, c32)):
+        for key in paths:  # the forward values, in list order, under the row rule (no median); the centre as a whole row
+            check_rows(f"{tag} camera {c} forward {key}", got[key], want[key], f32[key], failures, False, who, cap)
+    got, want, f32 = (path_gradients(l, c, ups, paths) for l, c in (kernel, (l64, c64), (l32, c32)))
+    for path in paths:
+        for k in NAMES:
+            check_rows(f"{tag} {path} -> {k}", got[path][k], want[path][k], f32[path][k], failures, median, who, cap)
+    return got, want, f32
+
+
+# ---- the edge rows -----------------------------------------------------------------------------------------------------------
+EDGE_ROWS = ("control", "depth 0.005", "depth just above 1e-2", "depth 0", "depth -2", "q = 0", "|q| = 1e-9", "|q| = 1e3", "needle",
+             "opacity +100", "opacity -inf", "zero SH", "covariance clamp")
+CLAMP_LOG_SCALE = 40.0
+EDGE_CULLED = ("depth 0", "depth -2")
+
+
+def _exact_zero(P, r, nonpositive=False):
+    """A float32 world point (x, 0, 0) whose camera coordinate r, x P[r,0] + P[r,3], is exactly 0 in float32 with the product
+    rounded first (the kernels: no contraction); nonpositive: and <= 0 where the product is fused into the sum."""
+    a, b = P[0, r, 0], P[0, r, 3]
+    x = -b / a
+    for _ in range(64):
+        x = torch.nextafter(x, torch.tensor(-float("inf")))
+    for _ in range(128):
+        x = torch.nextafter(x, torch.tensor(float("inf")))
+        if float(x * a + b) == 0.0 and (not nonpositive or float(x.double() * a.double() + b.double()) <= 0.0):
+            return torch.stack([x, torch.zeros(()), torch.zeros(())])
+    raise AssertionError("no float32 abscissa puts the coordinate at exactly 0")
+
+
+def edge_scene():
+    """Thirteen hand-built Gaussians in front of ring_cameras(1, 40, 30), placed in camera coordinates t and mapped back with
+    R^T (t - t0); 16 colour rows.  Every one is anisotropic with a generic quaternion unless its case is about the quaternion
+    (variance_q.grad would be analytically zero, round-off against round-off).
+      depth 0.005: on the optical axis, log scales about -9; kept, pz and zc clamped, the t[2] gradient branch off;
+      depth just above 1e-2: the branch on;  depth 0 (exactly) and depth -2: culled, all five gradient rows exactly zero;
+      q = 0: the rotation is the identity and the q gradient exactly zero;  |q| = 1e-9: clamped, the q gradient of order 1e7;
+      needle: log scales (0.5, -14, -14) at depth 9, its long axis along the camera's x: a box as long as the clamp allows,
+        and with 1e-6 on the diagonal lo = m - r of box_halfsize is round-off of either sign (m = 21.8, an ulp of 1.9e-6).
+        With cov_dilation = 0.3 the float32 formulation has it to 1.5e-5 of float64.  With 1e-6 (gcp_project) NO kept needle is
+        within float32's reach: kept means 3 sqrt(a) >= 1, a >= 0.11; the covariance is a rank-one matrix + 1e-6 I, so the
+        determinant 1e-6 (a + d) is what is left of a d - b c, two products rounded to 6e-8 of a d each: a relative error of
+        0.06 a d / (a + d) >= 1 % at best, here far more (the formulation's own gradients are 1 to 4 times off).  The row
+        rule's measured term is what carries its covariance path there;
+      opacity +100 / -inf: alpha exactly 1 / 0, opacity gradient 0;  zero SH: the sum is exactly 0, which the clamp passes;
+      covariance clamp: log scales (-2.5, CLAMP_LOG_SCALE, -3), q = (0, 0, 0, 1), mean (x, 0.3, 0).  The camera's P[0,0,1] is
+        an exact zero (ring_cameras: right = (0, -1, 0) x forward), so a scale on the world's y puts nothing into the first row
+        of the camera-space covariance, and x makes t[0] = x P00 + P03 an exact float32 zero, so J[2] = -0 keeps the rest of
+        it out of cov[0], cov[1], cov[2]: cov[3] alone passes FLT_MAX / 1000, is clamped and gets D[3] = 0, the determinant
+        a FLT_MAX / 1000 stays finite, and so does everything the float32 formulation returns (asserted without a GPU).  It
+        is cov[3], not cov[0], that can be clamped finitely: no entry of the rotation's second row is zero.  The float64
+        formulation differs on this row (its t[0] is the -1.7e-15 the product's rounding hid, times a 1e35 covariance), which
+        the rule's measured term absorbs: test_edge_rows therefore also holds the row to the float32 formulation itself,
+        and the log-scale gradient of the clamped axis to an exact zero.
+    The first twelve rows are drawn as before the last one was added."""
+    P, K, wh = ring_cameras(1, 40, 30)
+    R, t0 = P[0, :, :3].double(), P[0, :, 3].double()
+    g = torch.Generator().manual_seed(41)
+    n = 12  # the random rows; the covariance clamp is appended
+    row = {name: i for i, name in enumerate(EDGE_ROWS)}
+    t = torch.tensor([0.1, -0.05, 3.0], dtype=torch.float64).repeat(n, 1) + 0.2 * (torch.rand(n, 3, generator=g).double() - 0.5)
+    t[row["depth 0.005"]] = torch.tensor([0.0, 0.0, 0.005])
+    t[row["depth just above 1e-2"]] = torch.tensor([0.0005, -0.0005, 0.0101])
+    t[row["depth -2"], 2] = -2.0
+    t[row["needle"]] = torch.tensor([0.0, 0.75, 9.0])
+    mean = ((t - t0) @ R).float()  # R^T (t - t0)
+    mean[row["depth 0"]] = _exact_zero(P, 2, nonpositive=True)
+    q = torch.randn(n, 4, generator=g)
+    q = q / q.norm(dim=1, keepdim=True)
+    log_scale = torch.log(0.1 * (0.4 + 1.2 * torch.rand(n, 3, generator=g)))
+    for name in ("depth 0.005", "depth just above 1e-2"):
+        log_scale[row[name]] = torch.tensor([-9.0, -9.4, -8.7])
+    q[row["q = 0"]] = 0.0
+    q[row["|q| = 1e-9"]] *= 1e-9
+    q[row["|q| = 1e3"]] *= 1e3
+    # the needle's rotation is the camera's transposed: quaternion (x, y, z, w) of R^T
+    Rt = R.T
+    qw = 0.5 * torch.sqrt(1 + Rt[0, 0] + Rt[1, 1] + Rt[2, 2])
+    q[row["needle"]] = torch.stack([(Rt[2, 1] - Rt[1, 2]) / (4 * qw), (Rt[0, 2] - Rt[2, 0]) / (4 * qw), (Rt[1, 0] - Rt[0, 1]) / (4 * qw), qw]).float()
+    log_scale[row["needle"]] = torch.tensor([0.5, -14.0, -14.0])
+    opacity = torch.logit(0.1 + 0.8 * torch.rand(n, 1, generator=g))
+    opacity[row["opacity +100"]] = 100.0
+    opacity[row["opacity -inf"]] = -float("inf")
+    color = 0.5 * torch.randn(n, 16, 3, generator=g)
+    color[row["zero SH"]] = 0.0
+    assert float(P[0, 0, 1]) == 0.0
+    mean = torch.cat([mean, (_exact_zero(P, 0) + torch.tensor([0.0, 0.3, 0.0]))[None]])
+    q = torch.cat([q, torch.tensor([[0.0, 0.0, 0.0, 1.0]])])
+    log_scale = torch.cat([log_scale, torch.tensor([[-2.5, CLAMP_LOG_SCALE, -3.0]])])
+    opacity = torch.cat([opacity, torch.tensor([[0.3]])])
+    color = torch.cat([color, 0.5 * torch.randn(1, 16, 3, generator=g)])
+    return {"mean": mean, "variance_q": q, "variance_scale": log_scale, "opacity": opacity, "color": color, "P": P, "K": K, "wh": wh}, row
+
+
+def sub_world(w, first, n, n_basis):
+    """Gaussians first .. first + n - 1 of a world as a world of their own, the first n_basis colour rows."""
+    out = {k: w[k][first:first + n].clone() for k in NAMES}
+    out["color"] = out["color"][:, :n_basis].contiguous()
+    out.update(P=w["P"], K=w["K"], wh=w["wh"])
+    return out
+
+
+def position_config(family, n_basis):
+    degree = {1: 0, 4: 1, 9: 2, 16: 3}[n_basis]
+    return (family, ALL_SPLAT if family == "splat" else {}, degree, n_basis, "world", True)
+
+
+# ---- the tests ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("config", CONFIGS)
+@pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
+def test_rows_against_float64_one_upstream_at_a_time(shape, config, device):
+    """Forward values and all five parameter gradients of every path under the row rule, the exact zeros, the median check and
+    the cap on the inputs (the module's docstring).  On the MI355X: profiles/r11_projection_rows.md."""
+    cfg = CONFIGS[config]
+    w = world(shape, cfg[3])
+    leaves, cams, _ = run_kernels(w, cfg, device)
+    failures = []
+    check_case(f"{shape_id(shape)} {config}", w, cfg, (leaves, cams), failures)
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("family", EDGE_CONFIGS)
+def test_edge_rows(family, device):
+    """The hand-built scene through one kernel family at degree 3 in the world frame with depth: the row rule on every row
+    (no median: thirteen rows), what is kept and culled, the needle's integer box equal to the float32 formulation's, alpha
+    exactly 1 and 0, the zero colour sum passing its gradient, and the clamped covariance entry passing none."""
+    cfg = EDGE_CONFIGS[family]
+    w, row = edge_scene()
+    leaves, cams, grad_iter = run_kernels(w, cfg, device)
+    index = cams[0]["index"].cpu()
+    kept = set(index.tolist())
+    assert kept == {row[k] for k in EDGE_ROWS if k not in EDGE_CULLED}, kept
+    assert grad_iter.cpu().tolist() == [k not in EDGE_CULLED for k in EDGE_ROWS]
+    failures = []
+    got, want, f32 = check_case(f"edge {family}", w, cfg, (leaves, cams), failures, median=False, cap=False)
+    # the covariance clamp: float64 is no reference there (edge_scene), so the row is also held to the float32 formulation
+    # itself, at the project's rtol 2e-4 of the row (measured on the kernels' source compiled for the CPU: 1e-7; with
+    # sdot / det^2 in the backward, where det^2 overflowed to inf, these rows came out 1e-36 where the formulation has 1)
+    i = row["covariance clamp"]
+    for path in got:
+        for k in NAMES:
+            a, b = got[path][k][i], f32[path][k][i]
+            print("edge", family, "covariance clamp", path, "->", k, "kernel", a.tolist()[:4], "float32 formulation", b.tolist()[:4])
+            if not float((a - b).abs().max()) <= RTOL * float(b.abs().max()):
+                failures.append(f"edge {family} covariance clamp {path} -> {k}: kernel {a.tolist()[:6]} float32 formulation {b.tolist()[:6]}")
+    for path in got:
+        for k in NAMES:
+            assert torch.isfinite(got[path][k]).all(), (path, k)
+            for name in EDGE_CULLED:
+                assert float(got[path][k][row[name]].abs().max()) == 0.0, (path, k, name)
+        assert float(got[path]["variance_q"][row["q = 0"]].abs().max()) == 0.0, path
+        assert float(got[path]["opacity"][row["opacity +100"]].abs().max()) == 0.0, path
+        assert float(got[path]["opacity"][row["opacity -inf"]].abs().max()) == 0.0, path
+        # the covariance clamp: the clamped entry passes nothing to the scale that made it
+        assert float(got[path]["variance_scale"][row["covariance clamp"]][1]) == 0.0, path
+    r = {int(i): k for k, i in enumerate(index.tolist())}[row["covariance clamp"]]
+    vinv = cams[0]["variance_inverse"].detach().cpu().reshape(-1, 4)[r]
+    print("edge", family, "covariance clamp: variance_inverse", vinv.tolist())
+    assert float(vinv[3]) == pytest.approx(1000 / torch.finfo(torch.float32).max, rel=1e-5) and float(vinv[0]) > 0
+    assert float(got["variance_inverse"]["variance_scale"][row["covariance clamp"]].abs().max()) > 0
+    clamped = [float(g["variance_inverse"]["variance_q"][row["|q| = 1e-9"]].abs().max()) for g in (got, want)]
+    print("edge", family, "|q| = 1e-9: largest entry of its variance_q.grad row: kernel, float64", clamped)
+    assert clamped[1] > 1e5  # the float64 row is what a norm clamped to 1e-8 makes of it; the rule has compared the kernel's
+    list_row = {int(i): r for r, i in enumerate(index.tolist())}
+    alpha = cams[0]["opacity"].detach().cpu()
+    assert float(alpha[list_row[row["opacity +100"]]]) == 1.0 and float(alpha[list_row[row["opacity -inf"]]]) == 0.0
+    # the needle's box: the float32 formulation's own (fixed=None), integer for integer
+    _, own = run_formulation(w, cfg, torch.float32)
+    own_row = {int(i): r for r, i in enumerate(own[0]["index"].tolist())}
+    for key in ("startpoint", "endpoint"):
+        a, b = cams[0][key].cpu()[list_row[row["needle"]]], own[0][key][own_row[row["needle"]]]
+        print("edge", family, "needle", key, a.tolist(), b.tolist())
+        assert torch.equal(a, b.to(a.dtype)), key
+    # zero SH: l_d is exactly 0 and color.grad of the l_d path is g B_k (the float64 row is not zero, the rule has compared it)
+    assert float(cams[0]["l_d"].detach().cpu()[list_row[row["zero SH"]]].abs().max()) == 0.0
+    assert float(want["l_d"]["color"][row["zero SH"]].abs().max()) > 0 and float(got["l_d"]["color"][row["zero SH"]].abs().max()) > 0
+    assert not failures, "\n".join(failures)
+
+
+_REFERENCE = {}
+
+
+def all_upstreams_run(w, config, ups, device, offset=None):
+    """Forward and backward with all upstreams at once -> ({key: list tensor} of camera 0, {parameter: gradient}).
+    offset: the five parameters are views at that storage offset (in elements) into larger buffers."""
+    _, options, degree, _, frame, with_depth = config
+    leaves = {}
+    for k in NAMES:
+        src = w[k].to(device)
+        if offset is None:
+            leaves[k] = src.clone().requires_grad_(True)
+        else:
+            buf = torch.zeros(src.numel() + 8, device=device)
+            view = buf[offset:offset + src.numel()].view(src.shape)
+            view.copy_(src)
+            assert view.data_ptr() % 16 == 4 * offset and view.is_contiguous()
+            leaves[k] = view.requires_grad_(True)
+    cams, _, _ = gm.camera_inputs(*(leaves[k] for k in NAMES), w["P"].to(device), w["K"].to(device), w["wh"].to(device), TILE_LOGIT,
+                                  L_max=degree, sh_frame=frame, with_depth=with_depth, **options)
+    cam = cams[0]
+    assert cam is not None
+    loss = 0
+    for path in paths_of(config):
+        loss = loss + (cam[path] * ups[path][0].to(device)[cam["index"]]).sum()
+    grads = torch.autograd.grad(loss, [leaves[k] for k in NAMES])
+    return {k: v.detach() for k, v in cam.items()}, dict(zip(NAMES, grads))
+
+
+def reference_run(family, n_basis, device):
+    """The 259-Gaussian world through one family at n_basis stored colour rows, once."""
+    if (family, n_basis) not in _REFERENCE:
+        w = world(SHAPES[0], 16)
+        cfg = position_config(family, n_basis)
+        ups = upstreams(w, cfg, seed=3)
+        _REFERENCE[family, n_basis] = (ups, *all_upstreams_run(sub_world(w, 0, BIG, n_basis), cfg, ups, device))
+    return _REFERENCE[family, n_basis]
+
+
+@pytest.mark.parametrize("family", ("project", "splat"))
+@pytest.mark.parametrize("n_basis", BASES)
+@pytest.mark.parametrize("n", SIZES)
+def test_rows_do_not_depend_on_their_position(n, n_basis, family, device):
+    """Gaussians 258 - n .. 257 of the 259-Gaussian world (257 is kept by both families) as a world of their own (another block, another lane, another tail
+    length of the staging code): every output row and every gradient row BIT-EQUAL to the row the same Gaussian gets as a
+    member of the large world.  A thread's arithmetic does not depend on its position, so no tolerance."""
+    ups, big, big_grads = reference_run(family, n_basis, device)
+    first = BIG - 1 - n
+    cfg = position_config(family, n_basis)
+    w = sub_world(world(SHAPES[0], 16), first, n, n_basis)
+    small, grads = all_upstreams_run(w, cfg, {k: v[:, first:first + n] for k, v in ups.items()}, device)
+    member = (big["index"] >= first) & (big["index"] < first + n)
+    assert torch.equal(big["index"][member] - first, small["index"])  # the same Gaussians kept, in the same order
+    assert set(small) == set(big)
+    for k in small:
+        if k != "index":
+            assert small[k].dtype == big[k].dtype and torch.equal(small[k], big[k][member]), k
+    for k in NAMES:
+        assert torch.equal(grads[k], big_grads[k][first:first + n]), k
+
+
+@pytest.mark.parametrize("family", ("project", "splat"))
+@pytest.mark.parametrize("offset", (1, 2, 3))
+def test_parameter_arrays_need_only_four_byte_alignment(offset, family, device):
+    """The five parameters as views `offset` elements into larger buffers (copy_rows then reads them word by word): outputs
+    and gradients bit-equal to the same call on aligned copies."""
+    ups, want, want_grads = reference_run(family, 16, device)
+    w = sub_world(world(SHAPES[0], 16), 0, BIG, 16)
+    got, grads = all_upstreams_run(w, position_config(family, 16), ups, device, offset=offset)
+    assert set(got) == set(want)
+    for k in got:
+        assert got[k].dtype == want[k].dtype and torch.equal(got[k], want[k]), k
+    for k in NAMES:
+        assert torch.equal(grads[k], want_grads[k]), k

@@ -21,7 +21,7 @@ ILIM = torch.iinfo(torch.int32).max / 1000
 
 
 def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max, sh, cov_eps=1e-6, clamp_colour=False,
-                fixed=None):
+                fixed=None, centres="subpixel"):
     """oracle/gs_forward_torch.camera_inputs (its helpers, its order of operations, any float dtype) with three changes:
       * the centre stays a float, c = clamp(mean_pixel) + 0.5, and the box goes around it: with h = min(3-sigma half extent,
         box clamp), columns ceil(cx - h) .. floor(cx + h), rows likewise; kept: depth > 0, box not empty, x0 < W, x1 > 0,
@@ -30,7 +30,13 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
       * clamp_colour: l_d.clamp(min=0).
     fixed = per camera (index, startpoint, endpoint) or None: lists and integer boxes taken from there instead (held fixed:
     the float64 runs differentiate the floats on the lists the kernels made).  Returns (cams, grad_iter); every cam also
-    holds "centre_all" (N, 2): the float centres of ALL Gaussians in their own order."""
+    holds "centre_all" (N, 2): the float centres of ALL Gaussians in their own order.
+    centres: "subpixel" as above; "pixel": the kernels of csrc/gcp_splat.hip asked for integer centres (c = clamp(mean_pixel),
+    no 0.5, the box rule above around it; the caller truncates "mean"); "project": csrc/gcp_project.hip, the rule of
+    oracle/gs_forward_torch.camera_inputs (m = trunc(c), b = trunc(min(half, box clamp)), box m - b .. m + b, kept: depth > 0,
+    b_x != 0, m_x - b_x < W, m_x + b_x > 0, m_y - b_y < H, m_y + b_y > 0), "mean" again the float c."""
+    if centres not in ("subpixel", "pixel", "project"):
+        raise ValueError(centres)
     dev, dt = mean.device, mean.dtype
     n, n_cam = mean.shape[0], P.shape[0]
     width, height = int(wh[0][0]), int(wh[0][1])
@@ -39,7 +45,7 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
     mean_camera = homo @ P.transpose(1, 2)
     pix_h = mean_camera @ K.transpose(1, 2)
     mean_pixel = pix_h[:, :, 0:2] / pix_h[:, :, 2][:, :, None].clamp_min(1e-2)
-    centre = mean_pixel.clamp(min=-ILIM, max=ILIM) + 0.5
+    centre = mean_pixel.clamp(min=-ILIM, max=ILIM) + (0.5 if centres == "subpixel" else 0.0)
 
     q = variance_q / torch.norm(variance_q, dim=1, keepdim=True).clamp_min(1e-8)
     rot = gft.qvec_to_rotmat_batch(q)
@@ -59,6 +65,10 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
     h = half.clamp(max=gft.box_clamp(torch.tensor([[width, height]]), tile_max_width, dev))
     lo = torch.ceil((centre.detach() - h).clamp(min=-ILIM, max=ILIM)).to(torch.int32)
     hi = torch.floor((centre.detach() + h).clamp(min=-ILIM, max=ILIM)).to(torch.int32)
+    nonempty = (hi >= lo).all(dim=-1)
+    if centres == "project":
+        m, b = centre.detach().to(torch.int32), h.to(torch.int32)
+        lo, hi, nonempty = m - b, m + b, b[..., 0] != 0
     lim = torch.tensor([width, height], device=dev, dtype=torch.int32)
     grad_iter = torch.zeros(n, device=dev, dtype=torch.bool)
     cams = []
@@ -66,8 +76,7 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
         if fixed is None:
             z = mean_camera[c, :, 2].detach()
             order = torch.argsort(z, stable=True)
-            keep = (z > 0) & (hi[c, :, 0] >= lo[c, :, 0]) & (hi[c, :, 1] >= lo[c, :, 1]) & (lo[c, :, 0] < width) & (hi[c, :, 0] > 0) \
-                & (lo[c, :, 1] < height) & (hi[c, :, 1] > 0)
+            keep = (z > 0) & nonempty[c] & (lo[c, :, 0] < width) & (hi[c, :, 0] > 0) & (lo[c, :, 1] < height) & (hi[c, :, 1] > 0)
             index = order[keep[order]]
             start = torch.minimum(lo[c, index].clamp(min=0), lim)
             end = torch.minimum(hi[c, index].clamp(min=0), lim)
