@@ -21,106 +21,30 @@
 // The arithmetic follows the reference's order of operations (matrix products accumulated left to right, k
 // ascending, no FMA contraction: the library is built with -ffp-contract=off) so that the integer boxes that come
 // out of float -> int32 truncation agree with the reference's.
+//
+// This file holds only the kernels and entry points.  The bodies (project_fwd, project_gather, project_bwd) and the checks
+// the entry points share are in gcp_project.hpp, which gcp_splat.hip instantiates a second time with its SPLAT switch set.
 #include "gcp_project.hpp"
-#include "grouped_cumprod_hip.h"
 
 namespace {
-
-// Per Gaussian, one 64-byte record (what the gather reads back in one piece), the sort key of its depth and the cull flag.
-//   record words: 0-3 box x0 y0 x1 y1 | 4-5 pixel mean | 6-9 Sigma'^-1 | 10 opacity | 11-13 colour | 14 camera depth | 15 unused
-
-// MAXDEG: the highest SH degree the instantiation can evaluate (sh_degree <= MAXDEG is the caller's to ensure).
-template <int MAXDEG, bool WORLD>
-__device__ __forceinline__ void project_fwd(
-    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
-    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
-    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp,
-    float4* __restrict__ record, int* __restrict__ sort_key, uint8_t* __restrict__ keep, int* __restrict__ row_of) {
-  extern __shared__ float s_stage[];
-  const ParamTile tile = param_tile(s_stage, n_basis);
-  const Camera cam = load_camera(cam_P, cam_K);
-  for (i64 base = (i64)blockIdx.x * kThreads; base < n; base += (i64)gridDim.x * kThreads) {
-    const int cnt = (int)min((i64)kThreads, n - base);
-    __syncthreads();  // the previous chunk's rows are no longer read
-    load_param_tile(tile, mean, q, log_scale, color, base, cnt, n_basis);
-    __syncthreads();
-    const i64 i = base + threadIdx.x;
-    if (i >= n) continue;
-    Projected p;
-    project_one(cam, tile.mean, tile.q, tile.ls, threadIdx.x, p);
-    float hx, hy;
-    box_halfsize(p.a, p.c, p.d, hx, hy);
-    const float ilim = 2147483647.f / 1000.f;
-    const int mx = trunc_i32(clampf(p.px, -ilim, ilim)), my = trunc_i32(clampf(p.py, -ilim, ilim));
-    const int bw = trunc_i32(fminf(hx, box_clamp)), bh = trunc_i32(fminf(hy, box_clamp));
-    const bool k = p.t[2] > 0.f && bw != 0 && mx - bw < width && mx + bw > 0 && my - bh < height && my + bh > 0;
-    const int x0 = min(max(mx - bw, 0), width), y0 = min(max(my - bh, 0), height);
-    const int x1 = min(max(mx + bw, 0), width), y1 = min(max(my + bh, 0), height);
-    keep[i] = k ? 1 : 0;
-    row_of[i] = -1;
-    // kept depths are positive floats: their bit patterns sort like the values; culled Gaussians sort last
-    sort_key[i] = k ? __float_as_int(p.t[2]) : 0x7fffffff;
-    const float* sh = tile.sh + threadIdx.x * n_basis * 3;
-    float dir[3];
-    sh_direction<WORLD>(cam.P, p.view, dir);
-    const float x = dir[0], y = dir[1], z = dir[2];
-    float l[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) l[ch] = sh_colour<MAXDEG>(sh, ch, sh_degree, x, y, z);
-    const float alpha = 1.f / (1.f + expf(-opacity[i]));
-    float4* rec = record + 4 * i;
-    rec[0] = make_float4(__int_as_float(x0), __int_as_float(y0), __int_as_float(x1), __int_as_float(y1));
-    rec[1] = make_float4(__int_as_float(mx), __int_as_float(my), p.d / p.det, -p.b / p.det);
-    rec[2] = make_float4(-p.c / p.det, p.a / p.det, alpha, l[0]);
-    rec[3] = make_float4(l[1], l[2], p.t[2], 0.f);
-  }
-}
 
 #define GCP_PROJECT_FWD_PARAMS                                                                                              \
   const float *__restrict__ mean, const float *__restrict__ q, const float *__restrict__ log_scale,                        \
       const float *__restrict__ opacity, const float *__restrict__ color, const float *__restrict__ cam_P,                 \
       const float *__restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp,          \
       float4 *__restrict__ record, int *__restrict__ sort_key, uint8_t *__restrict__ keep, int *__restrict__ row_of
-#define GCP_PROJECT_FWD_ARGS \
-  mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, width, height, box_clamp, record, sort_key, keep, row_of
+// project_fwd without SPLAT: 1e-6 on the covariance's diagonal, no offset, no colour clamp
+#define GCP_PROJECT_FWD_ARGS                                                                                                 \
+  mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, width, height, box_clamp, 1e-6f, 0.f, false, record, sort_key, \
+      keep, row_of
 
 // degree <= 2 on the camera-frame direction: what every call ran before degree 3 and the world frame existed
-__global__ __launch_bounds__(kThreads) void k_project_fwd(GCP_PROJECT_FWD_PARAMS) { project_fwd<2, false>(GCP_PROJECT_FWD_ARGS); }
+__global__ __launch_bounds__(kThreads) void k_project_fwd(GCP_PROJECT_FWD_PARAMS) { project_fwd<2, false, false>(GCP_PROJECT_FWD_ARGS); }
 
 // <2, true>: degree <= 2, world frame; <3, false> and <3, true>: degree 3
 template <int MAXDEG, bool WORLD>
 __global__ __launch_bounds__(kThreads) void k_project_fwd_sh(GCP_PROJECT_FWD_PARAMS) {
-  project_fwd<MAXDEG, WORLD>(GCP_PROJECT_FWD_ARGS);
-}
-
-// Row r of the depth-ordered list is Gaussian perm[r]: unpack its record into the Function's argument arrays (DEPTH: and its
-// camera depth, 0 for a culled one).
-template <bool DEPTH>
-__device__ __forceinline__ void project_gather(
-    const float4* __restrict__ record, const int* __restrict__ perm, i64 m, int* __restrict__ start_xy,
-    int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
-    float* __restrict__ alpha, float* __restrict__ l_d, float* __restrict__ depth, i64* __restrict__ index, int* __restrict__ row_of,
-    const unsigned char* __restrict__ keep) {
-  for (i64 r = (i64)blockIdx.x * kThreads + threadIdx.x; r < m; r += (i64)gridDim.x * kThreads) {
-    const int i = perm[r];
-    const float4* rec = record + 4 * (i64)i;
-    const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
-    int x0 = __float_as_int(a.x), y0 = __float_as_int(a.y), x1 = __float_as_int(a.z), y1 = __float_as_int(a.w);
-    // `keep` given (the list holds ALL Gaussians, no kept count was read back): a culled one stays in the list behind
-    // the kept ones with an EMPTY box — binned into no tile, blended nowhere, zero gradients (its row_of stays -1)
-    const bool culled = keep != nullptr && keep[i] == 0;
-    if (culled) { x0 = 1; y0 = 1; x1 = 0; y1 = 0; }
-    reinterpret_cast<int2*>(start_xy)[r] = make_int2(x0, y0);
-    reinterpret_cast<int2*>(end_xy)[r] = make_int2(x1, y1);
-    reinterpret_cast<int2*>(mean_xy)[r] = make_int2(__float_as_int(b.x), __float_as_int(b.y));
-    boxsize[r] = (i64)(x1 - x0 + 1) * (i64)(y1 - y0 + 1);
-    reinterpret_cast<float4*>(vinv)[r] = make_float4(b.z, b.w, c.x, c.y);
-    alpha[r] = c.z;
-    l_d[3 * r] = c.w, l_d[3 * r + 1] = d.x, l_d[3 * r + 2] = d.y;
-    if (DEPTH) depth[r] = culled ? 0.f : d.z;
-    index[r] = i;
-    if (!culled) row_of[i] = (int)r;
-  }
+  project_fwd<MAXDEG, WORLD, false>(GCP_PROJECT_FWD_ARGS);
 }
 
 __global__ __launch_bounds__(kThreads) void k_project_gather(
@@ -128,7 +52,8 @@ __global__ __launch_bounds__(kThreads) void k_project_gather(
     int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
     float* __restrict__ alpha, float* __restrict__ l_d, i64* __restrict__ index, int* __restrict__ row_of,
     const unsigned char* __restrict__ keep) {
-  project_gather<false>(record, perm, m, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, nullptr, index, row_of, keep);
+  project_gather<int2, GatherDepth::no>(record, perm, m, start_xy, end_xy, reinterpret_cast<int2*>(mean_xy), boxsize, vinv, alpha, l_d,
+                                        nullptr, index, row_of, keep);
 }
 
 __global__ __launch_bounds__(kThreads) void k_project_gather_depth(
@@ -136,7 +61,8 @@ __global__ __launch_bounds__(kThreads) void k_project_gather_depth(
     int* __restrict__ end_xy, int* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
     float* __restrict__ alpha, float* __restrict__ l_d, float* __restrict__ depth, i64* __restrict__ index, int* __restrict__ row_of,
     const unsigned char* __restrict__ keep) {
-  project_gather<true>(record, perm, m, start_xy, end_xy, mean_xy, boxsize, vinv, alpha, l_d, depth, index, row_of, keep);
+  project_gather<int2, GatherDepth::yes>(record, perm, m, start_xy, end_xy, reinterpret_cast<int2*>(mean_xy), boxsize, vinv, alpha, l_d,
+                                         depth, index, row_of, keep);
 }
 
 #define GCP_PROJECT_BWD_PARAMS                                                                                              \
@@ -171,19 +97,16 @@ int project_forward_call(const float* mean, const float* quat_xyzw, const float*
                          const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
                          int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float* record,
                          int32_t* sort_key, uint8_t* keep, int32_t* row_of, void* stream) {
-  if (n_gauss < 0 || n_gauss > 0x7fffffff || !sh_arguments_valid(sh_degree, n_basis, sh_frame) || width < 0 || height < 0)
-    return GCP_ERR_INVALID_ARGUMENT;
-  if (n_gauss == 0) return GCP_OK;
-  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !record || !sort_key || !keep ||
-      !row_of || ((uintptr_t)record & 15))
-    return GCP_ERR_INVALID_ARGUMENT;
-  const size_t lds_fwd = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
-  if (lds_fwd > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
-  const bool deg3 = sh_degree > 2, world = sh_frame == 1;
-  auto kernel = deg3 ? (world ? k_project_fwd_sh<3, true> : k_project_fwd_sh<3, false>) : (world ? k_project_fwd_sh<2, true> : k_project_fwd);
-  hipLaunchKernelGGL(kernel, dim3(grid_for(n_gauss)), dim3(kThreads), lds_fwd, (hipStream_t)stream, mean, quat_xyzw, log_scale,
-                     opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, (int)width, (int)height,
-                     box_clamp, (float4*)record, sort_key, keep, row_of);
+  const int rc = check_projection_call(n_gauss <= 0x7fffffff && width >= 0 && height >= 0,
+                                       {mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K}, n_gauss, sh_degree, n_basis,
+                                       sh_frame, {record, sort_key, keep, row_of});
+  if (rc != kLaunch) return rc;
+  if ((uintptr_t)record & 15) return GCP_ERR_INVALID_ARGUMENT;
+  auto kernel = pick_kernel(sh_degree, sh_frame, k_project_fwd, k_project_fwd_sh<2, true>, k_project_fwd_sh<3, false>,
+                            k_project_fwd_sh<3, true>);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n_gauss)), dim3(kThreads), stage_bytes(n_basis), (hipStream_t)stream, mean, quat_xyzw,
+                     log_scale, opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, (int)width,
+                     (int)height, box_clamp, (float4*)record, sort_key, keep, row_of);
   GCP_HIP(hipGetLastError());
   return GCP_OK;
 }
@@ -237,28 +160,21 @@ int project_backward_call(const float* mean, const float* quat_xyzw, const float
                           int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
                           const float* grad_l_d, const float* grad_depth, bool with_depth, float* grad_mean, float* grad_quat,
                           float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
-  if (n_gauss < 0 || !sh_arguments_valid(sh_degree, n_basis, sh_frame)) return GCP_ERR_INVALID_ARGUMENT;
-  if (n_gauss == 0) return GCP_OK;
-  if (!mean || !quat_xyzw || !log_scale || !opacity_logit || !sh_coeff || !cam_P || !cam_K || !row_of || !grad_mean ||
-      !grad_quat || !grad_log_scale || !grad_opacity_logit || !grad_sh_coeff)
-    return GCP_ERR_INVALID_ARGUMENT;  // the upstream arrays may be NULL when no Gaussian was kept
-  const size_t lds = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
-  if (lds > 64 * 1024) return GCP_ERR_INVALID_ARGUMENT;  // n_basis <= 18
+  // the upstream arrays may be NULL when no Gaussian was kept
+  const int rc = check_projection_call(true, {mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K}, n_gauss, sh_degree,
+                                       n_basis, sh_frame, {row_of, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff});
+  if (rc != kLaunch) return rc;
   const dim3 grid(grid_for(n_gauss)), block(kThreads);
-  const bool deg3 = sh_degree > 2, world = sh_frame == 1;
-  if (!deg3 && !world) {
-    if (with_depth)
-      hipLaunchKernelGGL(k_project_bwd_depth, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff,
-                         cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth,
-                         grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);
-    else
-      hipLaunchKernelGGL(k_project_bwd, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P,
-                         cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_mean, grad_quat,
-                         grad_log_scale, grad_opacity_logit, grad_sh_coeff);
+  const size_t lds = stage_bytes(n_basis);
+  if (sh_degree <= 2 && sh_frame == 0 && !with_depth) {  // the one kernel without the g_depth argument
+    hipLaunchKernelGGL(k_project_bwd, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P,
+                       cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_mean, grad_quat,
+                       grad_log_scale, grad_opacity_logit, grad_sh_coeff);
   } else {
-    auto kernel = deg3 ? (world ? (with_depth ? k_project_bwd_sh<3, true, true> : k_project_bwd_sh<3, true, false>)
-                                : (with_depth ? k_project_bwd_sh<3, false, true> : k_project_bwd_sh<3, false, false>))
-                       : (with_depth ? k_project_bwd_sh<2, true, true> : k_project_bwd_sh<2, true, false>);
+    auto kernel = pick_kernel(sh_degree, sh_frame, k_project_bwd_depth,  // degree <= 2, camera frame: here only with depth
+                              with_depth ? k_project_bwd_sh<2, true, true> : k_project_bwd_sh<2, true, false>,
+                              with_depth ? k_project_bwd_sh<3, false, true> : k_project_bwd_sh<3, false, false>,
+                              with_depth ? k_project_bwd_sh<3, true, true> : k_project_bwd_sh<3, true, false>);
     hipLaunchKernelGGL(kernel, grid, block, lds, (hipStream_t)stream, mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K,
                        (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth, grad_mean,
                        grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff);

@@ -1,9 +1,15 @@
-// gcp_project.hpp — device code of the per-Gaussian camera projection that gcp_project.hip (integer centres) and
-// gcp_splat.hip (float centres, covariance dilation, colour clamp) share: the camera, the chain of one Gaussian
-// (project_one), the LDS staging of the parameter rows, the 3-sigma box, the SH colour and the backward chain.
-// Every function is inlined into the kernels of the including file; nothing here is a kernel.
+// gcp_project.hpp — the per-Gaussian camera projection, written once for its two families of kernels: gcp_project.hip
+// (integer centres, the reference's conventions) and gcp_splat.hip (float centres, covariance dilation, colour clamp).
+// Device side: the camera, the chain of one Gaussian (project_one), the LDS staging of the parameter rows, the 3-sigma box,
+// the SH colour, and the three bodies — project_fwd, project_gather, project_bwd — in which the compile-time switch SPLAT
+// selects the few lines the families differ in.  Host side: the checks and the kernel pick their entry points share.
+// Every function is inlined into the kernels and entry points of the including file; nothing here is a kernel.
 #pragma once
+#include <initializer_list>
+#include <type_traits>
+
 #include "gcp_device.hpp"
+#include "grouped_cumprod_hip.h"
 
 namespace {
 
@@ -208,7 +214,113 @@ __device__ __forceinline__ float sh_colour(const float* sh, int ch, int sh_degre
   return v;
 }
 
-// One thread per Gaussian, in the Gaussians' own order (coalesced parameter reads and gradient writes); the only
+// Forward, one thread per Gaussian.  Per Gaussian, one 64-byte record (what the gather reads back in one piece), the sort key
+// of its depth and the cull flag.
+//   record words: 0-3 box x0 y0 x1 y1 | 4-5 pixel centre (SPLAT: float, else int) | 6-9 Sigma'^-1 | 10 opacity | 11-13 colour |
+//                 14 camera depth | 15 unused
+// MAXDEG: the highest SH degree the instantiation can evaluate (sh_degree <= MAXDEG is the caller's to ensure).
+// SPLAT (gcp_splat.hip; false: cov_eps, mean_offset and clamp_colour are not read): the centre stays a float, stored as
+// px + mean_offset, and the box goes around it, ceil(c - h) .. floor(c + h); cov_eps replaces the 1e-6 on the covariance's
+// diagonal; clamp_colour: l = max(SH sum, 0) per channel.
+template <int MAXDEG, bool WORLD, bool SPLAT>
+__device__ __forceinline__ void project_fwd(
+    const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
+    const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
+    const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp, float cov_eps,
+    float mean_offset, bool clamp_colour, float4* __restrict__ record, int* __restrict__ sort_key, uint8_t* __restrict__ keep,
+    int* __restrict__ row_of) {
+  extern __shared__ float s_stage[];
+  const ParamTile tile = param_tile(s_stage, n_basis);
+  const Camera cam = load_camera(cam_P, cam_K);
+  for (i64 base = (i64)blockIdx.x * kThreads; base < n; base += (i64)gridDim.x * kThreads) {
+    const int cnt = (int)min((i64)kThreads, n - base);
+    __syncthreads();  // the previous chunk's rows are no longer read
+    load_param_tile(tile, mean, q, log_scale, color, base, cnt, n_basis);
+    __syncthreads();
+    const i64 i = base + threadIdx.x;
+    if (i >= n) continue;
+    Projected p;
+    project_one(cam, tile.mean, tile.q, tile.ls, threadIdx.x, p, SPLAT ? cov_eps : 1e-6f);
+    float hx, hy;
+    box_halfsize(p.a, p.c, p.d, hx, hy);
+    const float ilim = 2147483647.f / 1000.f;
+    bool k;                  // kept: in front of the camera, a box that is not empty and reaches into the frame
+    int x0, y0, x1, y1;      // the box, cut to the frame
+    float centre[2];         // words 4-5 of the record
+    if constexpr (SPLAT) {
+      const float cx = clampf(p.px, -ilim, ilim) + mean_offset, cy = clampf(p.py, -ilim, ilim) + mean_offset;
+      const float bw = fminf(hx, box_clamp), bh = fminf(hy, box_clamp);
+      // clamped before conversion: every operand of the tests below is a valid int32 (a NaN extent clamps to +-ilim)
+      const int bx0 = (int)ceilf(clampf(cx - bw, -ilim, ilim)), bx1 = (int)floorf(clampf(cx + bw, -ilim, ilim));
+      const int by0 = (int)ceilf(clampf(cy - bh, -ilim, ilim)), by1 = (int)floorf(clampf(cy + bh, -ilim, ilim));
+      k = p.t[2] > 0.f && bx1 >= bx0 && by1 >= by0 && bx0 < width && bx1 > 0 && by0 < height && by1 > 0;
+      x0 = min(max(bx0, 0), width), y0 = min(max(by0, 0), height);
+      x1 = min(max(bx1, 0), width), y1 = min(max(by1, 0), height);
+      centre[0] = cx, centre[1] = cy;  // finite for every Gaussian: clamped before the offset
+    } else {
+      const int mx = trunc_i32(clampf(p.px, -ilim, ilim)), my = trunc_i32(clampf(p.py, -ilim, ilim));
+      const int bw = trunc_i32(fminf(hx, box_clamp)), bh = trunc_i32(fminf(hy, box_clamp));
+      k = p.t[2] > 0.f && bw != 0 && mx - bw < width && mx + bw > 0 && my - bh < height && my + bh > 0;
+      x0 = min(max(mx - bw, 0), width), y0 = min(max(my - bh, 0), height);
+      x1 = min(max(mx + bw, 0), width), y1 = min(max(my + bh, 0), height);
+      centre[0] = __int_as_float(mx), centre[1] = __int_as_float(my);
+    }
+    keep[i] = k ? 1 : 0;
+    row_of[i] = -1;
+    // kept depths are positive floats: their bit patterns sort like the values; culled Gaussians sort last
+    sort_key[i] = k ? __float_as_int(p.t[2]) : 0x7fffffff;
+    const float* sh = tile.sh + threadIdx.x * n_basis * 3;
+    float dir[3];
+    sh_direction<WORLD>(cam.P, p.view, dir);
+    float l[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      l[ch] = sh_colour<MAXDEG>(sh, ch, sh_degree, dir[0], dir[1], dir[2]);
+      if constexpr (SPLAT)
+        if (clamp_colour && l[ch] < 0.f) l[ch] = 0.f;  // the test the backward repeats on the same sum
+    }
+    const float alpha = 1.f / (1.f + expf(-opacity[i]));
+    float4* rec = record + 4 * i;
+    rec[0] = make_float4(__int_as_float(x0), __int_as_float(y0), __int_as_float(x1), __int_as_float(y1));
+    rec[1] = make_float4(centre[0], centre[1], p.d / p.det, -p.b / p.det);
+    rec[2] = make_float4(-p.c / p.det, p.a / p.det, alpha, l[0]);
+    rec[3] = make_float4(l[1], l[2], p.t[2], 0.f);
+  }
+}
+
+// Gather: row r of the depth-ordered list is Gaussian perm[r]; unpack its record into the Function's argument arrays, the
+// centre as the family's Centre (int2 or float2).  DEPTH: whether its camera depth is written too (0 for a culled one).
+enum class GatherDepth { no, yes, if_given };  // if_given: where `depth` is not NULL, tested at run time
+template <typename Centre, GatherDepth DEPTH>
+__device__ __forceinline__ void project_gather(
+    const float4* __restrict__ record, const int* __restrict__ perm, i64 m, int* __restrict__ start_xy,
+    int* __restrict__ end_xy, Centre* __restrict__ mean_xy, i64* __restrict__ boxsize, float* __restrict__ vinv,
+    float* __restrict__ alpha, float* __restrict__ l_d, float* __restrict__ depth, i64* __restrict__ index, int* __restrict__ row_of,
+    const unsigned char* __restrict__ keep) {
+  for (i64 r = (i64)blockIdx.x * kThreads + threadIdx.x; r < m; r += (i64)gridDim.x * kThreads) {
+    const int i = perm[r];
+    const float4* rec = record + 4 * (i64)i;
+    const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+    int x0 = __float_as_int(a.x), y0 = __float_as_int(a.y), x1 = __float_as_int(a.z), y1 = __float_as_int(a.w);
+    // `keep` given (the list holds ALL Gaussians, no kept count was read back): a culled one stays in the list behind
+    // the kept ones with an EMPTY box — binned into no tile, blended nowhere, zero gradients (its row_of stays -1)
+    const bool culled = keep != nullptr && keep[i] == 0;
+    if (culled) { x0 = 1; y0 = 1; x1 = 0; y1 = 0; }
+    reinterpret_cast<int2*>(start_xy)[r] = make_int2(x0, y0);
+    reinterpret_cast<int2*>(end_xy)[r] = make_int2(x1, y1);
+    if constexpr (std::is_same_v<Centre, int2>) mean_xy[r] = make_int2(__float_as_int(b.x), __float_as_int(b.y));
+    else mean_xy[r] = make_float2(b.x, b.y);
+    boxsize[r] = (i64)(x1 - x0 + 1) * (i64)(y1 - y0 + 1);
+    reinterpret_cast<float4*>(vinv)[r] = make_float4(b.z, b.w, c.x, c.y);
+    alpha[r] = c.z;
+    l_d[3 * r] = c.w, l_d[3 * r + 1] = d.x, l_d[3 * r + 2] = d.y;
+    if (DEPTH == GatherDepth::yes || (DEPTH == GatherDepth::if_given && depth != nullptr)) depth[r] = culled ? 0.f : d.z;
+    index[r] = i;
+    if (!culled) row_of[i] = (int)r;
+  }
+}
+
+// Backward, one thread per Gaussian, in the Gaussians' own order (coalesced parameter reads and gradient writes); the only
 // scattered reads are the 8 upstream gradient words of its row `row_of[i]` in the depth-ordered list.  Culled
 // Gaussians (row -1) get zeros: every gradient row is written, nothing needs clearing first.
 // SPLAT (gcp_splat.hip; false leaves the chain of gcp_project.hip as it is): cov_eps replaces the 1e-6 on the covariance's
@@ -227,18 +339,15 @@ __device__ __forceinline__ void project_bwd(
   // parameter rows come in and gradient rows go out through LDS as contiguous runs: straight from / to registers they are
   // 37 + 38 four-byte accesses per thread, 12-108 bytes apart (gradient rows direct: 365 us per 10^6 Gaussians; staged: 140)
   extern __shared__ float s_stage[];
-  float* s_mean = s_stage;
-  float* s_q = s_mean + 3 * kThreads;
-  float* s_ls = s_q + 4 * kThreads;
-  float* s_sh = s_ls + 3 * kThreads;
+  const ParamTile tile = param_tile(s_stage, n_basis);  // the gradient rows have the layout of the parameter rows: a thread's
+                                                         // parameter row is replaced, in place and by that thread alone, with its
+                                                         // gradient row
   const int sh_words = 3 * n_basis;
-  float* lm = s_mean + 3 * threadIdx.x;
-  float* lq = s_q + 4 * threadIdx.x;
-  float* lls = s_ls + 3 * threadIdx.x;
-  float* gsh = s_sh + sh_words * threadIdx.x;
+  float* lm = tile.mean + 3 * threadIdx.x;
+  float* lq = tile.q + 4 * threadIdx.x;
+  float* lls = tile.ls + 3 * threadIdx.x;
+  float* gsh = tile.sh + sh_words * threadIdx.x;
   const Camera cam = load_camera(cam_P, cam_K);
-  const ParamTile tile = param_tile(s_stage, n_basis);  // same layout as the gradient rows: a thread's parameter row is
-                                                         // replaced, in place and by that thread alone, with its gradient row
   for (i64 base = (i64)blockIdx.x * kThreads; base < n; base += (i64)gridDim.x * kThreads) {
     load_param_tile(tile, mean, q, log_scale, color, base, (int)min((i64)kThreads, n - base), n_basis);
     __syncthreads();
@@ -435,10 +544,10 @@ __device__ __forceinline__ void project_bwd(
     }  // kept Gaussian
     __syncthreads();
     const int cnt = (int)min((i64)kThreads, n - base);
-    for (int j = threadIdx.x; j < 3 * cnt; j += kThreads) grad_mean[3 * base + j] = s_mean[j], grad_log_scale[3 * base + j] = s_ls[j];
-    for (int j = threadIdx.x; j < 4 * cnt; j += kThreads) grad_q[4 * base + j] = s_q[j];
+    for (int j = threadIdx.x; j < 3 * cnt; j += kThreads) grad_mean[3 * base + j] = tile.mean[j], grad_log_scale[3 * base + j] = tile.ls[j];
+    for (int j = threadIdx.x; j < 4 * cnt; j += kThreads) grad_q[4 * base + j] = tile.q[j];
     float* out_sh = grad_color + base * sh_words;
-    for (int j = threadIdx.x; j < sh_words * cnt; j += kThreads) out_sh[j] = s_sh[j];
+    for (int j = threadIdx.x; j < sh_words * cnt; j += kThreads) out_sh[j] = tile.sh[j];
     __syncthreads();
   }
 }
@@ -448,6 +557,34 @@ inline int grid_for(i64 n) { return (int)((n + kThreads - 1) / kThreads < 65536 
 
 inline bool sh_arguments_valid(int32_t sh_degree, int32_t n_basis, int32_t sh_frame) {
   return sh_degree >= 0 && sh_degree <= 3 && n_basis >= (sh_degree + 1) * (sh_degree + 1) && (sh_frame == 0 || sh_frame == 1);
+}
+
+// LDS of one block of the forward and backward kernels: the ParamTile.  0: more than the 64 KiB a block can have (n_basis > 18).
+inline size_t stage_bytes(int32_t n_basis) {
+  const size_t bytes = (size_t)kThreads * (10 + 3 * (size_t)n_basis) * sizeof(float);
+  return bytes <= 64 * 1024 ? bytes : 0;
+}
+
+// What a forward or backward entry point checks before any HIP call, in the order the results depend on: the scalars
+// (`scalars_ok`: those of the entry point's own), nothing to do, the arrays it cannot do without (the seven parameter
+// arrays and `outputs`), the LDS.  kLaunch: go on; anything else is the entry point's return value.
+constexpr int kLaunch = -1;
+inline int check_projection_call(bool scalars_ok, const float* const (&params)[7], int64_t n_gauss, int32_t sh_degree, int32_t n_basis,
+                                 int32_t sh_frame, std::initializer_list<const void*> outputs) {
+  if (!scalars_ok || n_gauss < 0 || !sh_arguments_valid(sh_degree, n_basis, sh_frame)) return GCP_ERR_INVALID_ARGUMENT;
+  if (n_gauss == 0) return GCP_OK;
+  for (const float* p : params)
+    if (!p) return GCP_ERR_INVALID_ARGUMENT;
+  for (const void* p : outputs)
+    if (!p) return GCP_ERR_INVALID_ARGUMENT;
+  return stage_bytes(n_basis) ? kLaunch : GCP_ERR_INVALID_ARGUMENT;
+}
+
+// The instantiation of a call: degree <= 2 or degree 3, SH basis on camera-frame or world-space directions.
+template <typename Kernel>
+inline Kernel pick_kernel(int32_t sh_degree, int32_t sh_frame, Kernel deg2_camera, Kernel deg2_world, Kernel deg3_camera, Kernel deg3_world) {
+  const bool world = sh_frame == 1;
+  return sh_degree > 2 ? (world ? deg3_world : deg3_camera) : (world ? deg2_world : deg2_camera);
 }
 
 }  // namespace

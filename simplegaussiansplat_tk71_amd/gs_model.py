@@ -111,14 +111,21 @@ def _box_clamp(width, height, tile_max_width):
 
 
 class _ProjectCamera(torch.autograd.Function):
-    """One camera of `camera_inputs` on the HIP library (csrc/gcp_project.hip): gcp_project_forward, the library's
-    stable radix sort on the depth keys, gcp_project_gather; backward = gcp_project_backward.  with_depth: the camera-space
-    depths too, right after l_d (gcp_project_gather_depth / gcp_project_backward_depth).  `L_max` is the ACTIVE degree, which
-    may be below what `color` stores; `sh_frame` 0 / 1 = camera / world directions (the gcp_project_*_sh entry points)."""
+    """One camera of `camera_inputs` on the HIP library: the projection's forward kernel, the library's stable radix sort on
+    the depth keys, its gather; backward = its backward kernel.  `L_max` is the ACTIVE degree, which may be below what `color`
+    stores; `sh_frame` 0 / 1 = camera / world directions; with_depth: the camera-space depths too, right after l_d.
+    splat=None: the reference's conventions, on the kernels of csrc/gcp_project.hip (gcp_project_forward_sh,
+    gcp_project_gather or gcp_project_gather_depth, gcp_project_backward_sh); the centre is int32 (m, 2) without a gradient.
+    splat=(subpixel, cov_eps, clamp_colour): the kernels of csrc/gcp_splat.hip (gcp_splat_forward, gcp_splat_gather,
+    gcp_splat_backward): `cov_eps` on the diagonal of the pixel covariance, the SH colour clamped at 0 (`clamp_colour`), and —
+    `subpixel` — the pixel centre kept as float32 (m, 2) at px + 0.5, differentiable: its gradient is handed to the backward
+    as grad_mean_xy.  Not `subpixel`: the centre is truncated as by default and returned as int32 without a gradient (the box
+    still goes around the untruncated centre, by the rule of the float one).
+    Returns (vinv, alpha, l_d, [depth,] mean_xy, start, end, boxsize, index, keep)."""
 
     @staticmethod
     def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
-                capture_safe=False, with_depth=False, sh_frame=0):
+                capture_safe=False, with_depth=False, sh_frame=0, splat=None):
         dev, n = mean.device, mean.shape[0]
         args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
         for t in args:
@@ -127,98 +134,43 @@ class _ProjectCamera(torch.autograd.Function):
         if not mean.is_cuda:
             raise RuntimeError("the fused projection is a HIP kernel: tensors must live on the GPU (no CPU path)")
         lib = _lib.load()
+        subpixel = splat is not None and splat[0]
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
         record, sort_key, row_of = f32(n, 16), i32(n), i32(n)
         keep = torch.empty(n, dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.gcp_project_forward_sh(*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height,
-                                                  box_clamp, record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(),
-                                                  stream), "gcp_project_forward")
+            world = (*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height, box_clamp)
+            made = (record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream)
+            if splat is None:
+                _lib.check(lib.gcp_project_forward_sh(*world, *made), "gcp_project_forward")
+            else:
+                _lib.check(lib.gcp_splat_forward(*world, splat[1], 0.5 if subpixel else 0.0, int(splat[2]), *made), "gcp_splat_forward")
             # the one device->host read: sizes of the outputs.  capture_safe: none — the list keeps all n Gaussians, the
-            # culled ones behind the kept ones with empty boxes (gcp_project_gather with the keep mask)
+            # culled ones behind the kept ones with empty boxes (the gather with the keep mask)
             m = n if capture_safe else (int(keep.sum()) if n else 0)
             # culled Gaussians carry the largest key: the first m entries of the stable permutation are the kept ones in
             # depth order, ties in the Gaussians' own order
             perm = _raster.stable_sort_keys(sort_key, key_bits=31)[1] if n else sort_key
-            start, end, mean_xy, boxsize = i32(m, 2), i32(m, 2), i32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
-            vinv, alpha, l_d, index = f32(m, 2, 2), f32(m, 1), f32(m, 3), torch.empty(m, dtype=torch.int64, device=dev)
-            if with_depth:
-                depth = f32(m)
-                _lib.check(lib.gcp_project_gather_depth(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
-                                                        mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
-                                                        l_d.data_ptr(), depth.data_ptr(), index.data_ptr(), row_of.data_ptr(),
-                                                        keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather_depth")
-            else:
-                _lib.check(lib.gcp_project_gather(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
-                                                  mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
-                                                  l_d.data_ptr(), index.data_ptr(), row_of.data_ptr(),
-                                                  keep.data_ptr() if capture_safe else None, stream), "gcp_project_gather")
-        keep = keep.view(torch.bool)
-        ctx.save_for_backward(*args, row_of)
-        ctx.L_max, ctx.with_depth, ctx.sh_frame = L_max, with_depth, sh_frame
-        out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), start, end, mean_xy, boxsize, index, keep)
-        ctx.mark_non_differentiable(*out[-6:])
-        return out
-
-    @staticmethod
-    def backward(ctx, g_vinv, g_alpha, g_ld, *rest):
-        *args, row_of = ctx.saved_tensors
-        mean, variance_q, variance_scale, opacity, color = args[:5]
-        grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
-        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:1 if ctx.with_depth else 0])]
-        g_depth = g[3].data_ptr() if ctx.with_depth else None
-        with torch.cuda.device(mean.device):
-            stream = torch.cuda.current_stream(mean.device).cuda_stream
-            _lib.check(_lib.load().gcp_project_backward_sh(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1],
-                                                           ctx.sh_frame, row_of.data_ptr(), *(t.data_ptr() for t in g[:3]), g_depth,
-                                                           *(t.data_ptr() for t in grads), stream), "gcp_project_backward")
-        return (*grads, None, None, None, None, None, None, None, None, None)
-
-
-class _SplatCamera(torch.autograd.Function):
-    """`_ProjectCamera` on the kernels of csrc/gcp_splat.hip (gcp_splat_forward, the same sort, gcp_splat_gather;
-    backward = gcp_splat_backward): `cov_eps` on the diagonal of the pixel covariance, the SH colour clamped at 0
-    (`clamp_colour`), and — `subpixel` — the pixel centre kept as float32 (m, 2) at px + 0.5, differentiable: its gradient is
-    handed to the backward as grad_mean_xy.  Not `subpixel`: the centre is truncated as `_ProjectCamera` truncates it and
-    returned as int32 without a gradient (the box still goes around the untruncated centre, by the rule of the float one)."""
-
-    @staticmethod
-    def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
-                capture_safe, with_depth, sh_frame, subpixel, cov_eps, clamp_colour):
-        dev, n = mean.device, mean.shape[0]
-        args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
-        for t in args:
-            if t.dtype != torch.float32 or t.device != dev:
-                raise RuntimeError("projection expects float32 tensors on one device")
-        if not mean.is_cuda:
-            raise RuntimeError("the fused projection is a HIP kernel: tensors must live on the GPU (no CPU path)")
-        lib = _lib.load()
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        record, sort_key, row_of = f32(n, 16), i32(n), i32(n)
-        keep = torch.empty(n, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.gcp_splat_forward(*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height,
-                                             box_clamp, cov_eps, 0.5 if subpixel else 0.0, int(clamp_colour), record.data_ptr(),
-                                             sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream), "gcp_splat_forward")
-            m = n if capture_safe else (int(keep.sum()) if n else 0)  # as _ProjectCamera: the one device->host read
-            perm = _raster.stable_sort_keys(sort_key, key_bits=31)[1] if n else sort_key
-            start, end, mean_xy, boxsize = i32(m, 2), i32(m, 2), f32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
+            start, end, boxsize = i32(m, 2), i32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
+            mean_xy = i32(m, 2) if splat is None else f32(m, 2)
             vinv, alpha, l_d, index = f32(m, 2, 2), f32(m, 1), f32(m, 3), torch.empty(m, dtype=torch.int64, device=dev)
             depth = f32(m) if with_depth else None
-            _lib.check(lib.gcp_splat_gather(record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(),
-                                            mean_xy.data_ptr(), boxsize.data_ptr(), vinv.data_ptr(), alpha.data_ptr(),
-                                            l_d.data_ptr(), depth.data_ptr() if with_depth else None, index.data_ptr(),
-                                            row_of.data_ptr(), keep.data_ptr() if capture_safe else None, stream), "gcp_splat_gather")
-        if not subpixel:
+            lists = (record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(), mean_xy.data_ptr(), boxsize.data_ptr(),
+                     vinv.data_ptr(), alpha.data_ptr(), l_d.data_ptr())
+            rows = (index.data_ptr(), row_of.data_ptr(), keep.data_ptr() if capture_safe else None, stream)
+            if splat is not None:
+                _lib.check(lib.gcp_splat_gather(*lists, depth.data_ptr() if with_depth else None, *rows), "gcp_splat_gather")
+            elif with_depth:
+                _lib.check(lib.gcp_project_gather_depth(*lists, depth.data_ptr(), *rows), "gcp_project_gather_depth")
+            else:
+                _lib.check(lib.gcp_project_gather(*lists, *rows), "gcp_project_gather")
+        if splat is not None and not subpixel:
             mean_xy = mean_xy.to(torch.int32)  # towards zero, as the kernels of gcp_project.hip convert
         keep = keep.view(torch.bool)
         ctx.save_for_backward(*args, row_of)
-        ctx.L_max, ctx.with_depth, ctx.sh_frame = L_max, with_depth, sh_frame
-        ctx.subpixel, ctx.cov_eps, ctx.clamp_colour = subpixel, cov_eps, clamp_colour
+        ctx.L_max, ctx.with_depth, ctx.sh_frame, ctx.splat = L_max, with_depth, sh_frame, splat
         out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), mean_xy, start, end, boxsize, index, keep)
         ctx.mark_non_differentiable(*out[-(5 if subpixel else 6):])
         return out
@@ -227,17 +179,22 @@ class _SplatCamera(torch.autograd.Function):
     def backward(ctx, g_vinv, g_alpha, g_ld, *rest):
         *args, row_of = ctx.saved_tensors
         mean, variance_q, variance_scale, opacity, color = args[:5]
+        splat = ctx.splat
+        subpixel = splat is not None and splat[0]
         grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
-        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:int(ctx.with_depth) + int(ctx.subpixel)])]
+        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:int(ctx.with_depth) + int(subpixel)])]
         g_depth = g[3].data_ptr() if ctx.with_depth else None
-        g_mean_xy = g[-1].data_ptr() if ctx.subpixel else None
         with torch.cuda.device(mean.device):
-            stream = torch.cuda.current_stream(mean.device).cuda_stream
-            _lib.check(_lib.load().gcp_splat_backward(*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1],
-                                                      ctx.sh_frame, row_of.data_ptr(), *(t.data_ptr() for t in g[:3]), g_depth,
-                                                      ctx.cov_eps, int(ctx.clamp_colour), g_mean_xy, *(t.data_ptr() for t in grads),
-                                                      stream), "gcp_splat_backward")
-        return (*grads, *[None] * 12)
+            upstream = (*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1], ctx.sh_frame, row_of.data_ptr(),
+                        *(t.data_ptr() for t in g[:3]), g_depth)
+            made = (*(t.data_ptr() for t in grads), torch.cuda.current_stream(mean.device).cuda_stream)
+            lib = _lib.load()
+            if splat is None:
+                _lib.check(lib.gcp_project_backward_sh(*upstream, *made), "gcp_project_backward")
+            else:
+                _lib.check(lib.gcp_splat_backward(*upstream, splat[1], int(splat[2]), g[-1].data_ptr() if subpixel else None, *made),
+                           "gcp_splat_backward")
+        return (*grads, *[None] * 10)
 
 
 def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
@@ -279,20 +236,16 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
     if sh_frame not in SH_FRAMES:
         raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
     centres, cov_eps, clamp_colour = _splat_options(centres, cov_dilation, clamp_colour)
-    splat = centres != "pixel" or cov_dilation is not None or clamp_colour
+    # None: the defaults, on the kernels of csrc/gcp_project.hip
+    splat = (centres == "subpixel", cov_eps, clamp_colour) if centres != "pixel" or cov_dilation is not None or clamp_colour else None
     width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
     clamp = _box_clamp(width, height, tile_max_width)
     grad_iter = None
     cams = []
     for c in range(P.shape[0]):
-        if splat:
-            out = _SplatCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
-                                     capture_safe, with_depth, SH_FRAMES[sh_frame], centres == "subpixel", cov_eps, clamp_colour)
-            mean_xy, start, end, boxsize, index, keep = out[-6:]
-        else:
-            out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
-                                       capture_safe, with_depth, SH_FRAMES[sh_frame])
-            start, end, mean_xy, boxsize, index, keep = out[-6:]
+        out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
+                                   capture_safe, with_depth, SH_FRAMES[sh_frame], splat)
+        mean_xy, start, end, boxsize, index, keep = out[-6:]
         vinv, alpha, l_d = out[:3]
         grad_iter = keep if grad_iter is None else grad_iter | keep
         cam = None if index.numel() == 0 else {

@@ -283,6 +283,55 @@ def test_pixel_centres_with_a_dilation_stay_integers(device):
     assert float(leaves[2].grad.abs().max()) > 0
 
 
+FOLD_SHAPES = [(259, 64, 48), (1291, 64, 48)]  # one full block + 3 rows | five blocks + 11 rows (tests/test_projection_rows_gpu.py's counts)
+
+
+@pytest.mark.parametrize("frame", ("camera", "world"))
+@pytest.mark.parametrize("degree", (0, 2, 3))
+@pytest.mark.parametrize("shape", FOLD_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_both_families_run_one_forward_body(shape, degree, frame, device):
+    """gcp_project_forward_sh and gcp_splat_forward instantiate one body (csrc/gcp_project.hpp: project_fwd): with
+    cov_eps = 1e-6, mean_offset = 0 and no colour clamp the splat family computes the integer family's record bit for bit
+    (words 6-14: Sigma'^-1, opacity, colour, depth), its float centre truncates to the integer centre, and the sort key is
+    the same wherever both keep or both cull.  Only the box rule differs (ceil / floor around the float centre against
+    trunc(centre) +- trunc(half extent)), so `keep` may differ at the frame's edge and for boxes narrower than a pixel: it has
+    to agree on 95 % of the Gaussians, which only stops the comparison from running on nothing.  These worlds on the CPU (the
+    two rules in `formulation`, centres="pixel" against "project", float32): 256 of 259 agree (98.8 %) and 1273 of 1291
+    (98.6 %); a 40 x 30 frame, where many half extents are below a pixel, would not do (243 of 259, 93.8 %)."""
+    from simplegaussiansplat_tk71_amd import _lib
+
+    n, width, height = shape
+    n_basis = (degree + 1) ** 2
+    w = random_world(n, 1, width, height, 7 + n, device, n_basis=n_basis)
+    lib = _lib.load()
+    params = [w[k].contiguous() for k in NAMES] + [w["P"][0].contiguous(), w["K"][0].contiguous()]
+    clamp = gm._box_clamp(width, height, TILE_LOGIT)
+
+    def run(splat):
+        record = torch.empty(n, 16, dtype=torch.float32, device=device)
+        sort_key, row_of = (torch.empty(n, dtype=torch.int32, device=device) for _ in range(2))
+        keep = torch.empty(n, dtype=torch.uint8, device=device)
+        head = (*(t.data_ptr() for t in params), n, degree, n_basis, gm.SH_FRAMES[frame], width, height, clamp)
+        made = (record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        if splat:
+            _lib.check(lib.gcp_splat_forward(*head, 1e-6, 0.0, 0, *made), "gcp_splat_forward")
+        else:
+            _lib.check(lib.gcp_project_forward_sh(*head, *made), "gcp_project_forward_sh")
+        torch.cuda.synchronize()
+        return record, sort_key, keep.bool()
+
+    rec_i, key_i, keep_i = run(False)
+    rec_f, key_f, keep_f = run(True)
+    assert torch.equal(rec_i[:, 6:15].view(torch.int32), rec_f[:, 6:15].view(torch.int32))
+    assert torch.equal(rec_f[:, 4:6].to(torch.int32), rec_i[:, 4:6].view(torch.int32))
+    agree = keep_i == keep_f
+    share = float(agree.float().mean())
+    print(shape, degree, frame, "kept", int(keep_i.sum()), int(keep_f.sum()), "keep agrees on", int(agree.sum()), "of", n, share)
+    assert torch.equal(key_i[agree], key_f[agree])
+    assert int((keep_i & keep_f).sum()) > 0
+    assert share >= 0.95, share
+
+
 def small_model(device, **kw):
     n, width, height = 48, 24, 20
     w = random_world(n, 1, width, height, 23, device, sigma=0.12, n_basis=9)
