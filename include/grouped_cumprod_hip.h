@@ -650,6 +650,62 @@ int gcp_ssim_l1_backward(const float* img1, const float* img2, const float* dm_d
 int gcp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                   double beta2, double eps, int64_t step, void* stream);
 
+/* ---- the caller's density control on the device (csrc/gcp_densify.hip) ---------------------
+ * Split / clone / prune of gs_model.py:201-265 as one pass whose decisions are all taken from the state BEFORE it, each
+ * Gaussian taking one action, and which carries the optimiser's moments of the surviving rows along.  Every entry point
+ * validates before any HIP call (negative sizes, NULL with rows to process, a non-finite threshold or extent,
+ * n_split < 1: GCP_ERR_INVALID_ARGUMENT); n_gauss == 0 or n_rows == 0 is a no-op.  No value-carrying atomics: results
+ * are bit-identical whatever the launch shape.
+ *
+ * gcp_densify_accumulate: the screen-space statistic of one camera.  grad_xy f32[m,2] = d loss / d centre in list order
+ * (8-byte aligned), index i64[m] = the list's Gaussian ids.  Per entry: norm_acc[id] += sqrtf(gx^2 + gy^2) with
+ * gx = grad_xy[i][0] * scale_x, gy = grad_xy[i][1] * scale_y; view_count[id] += 1.  A Gaussian appears at most once in
+ * a camera's list, so the update uses no atomics.  An id outside [0, n_gauss) is never written through: the entry is
+ * skipped and the call still returns GCP_OK (the launch is asynchronous; nothing is read back).  n_bad (device int32, may
+ * be NULL, zeroed by the caller) counts such ids for a caller that wants to refuse them; norm_acc == view_count == NULL
+ * with n_bad: only that count, nothing accumulated — how gs_model.accumulate_screen_grads(validate=True) refuses a list as
+ * a whole before it adds anything.
+ *
+ * gcp_densify_plan: with g = norm_acc / max(view_count, 1), s = max_k exp(log_scale_k) and
+ * hot = view_count > 0 && g >= grad_threshold:
+ *     split  hot && s >  dense_extent   n_split fresh children of scale s / (0.8 n_split); the parent disappears
+ *     clone  hot && s <= dense_extent   2 rows: the survivor and one fresh copy
+ *     keep   otherwise                  1 row
+ * then the prune test on the OUTPUT rows: none is written if sigmoid(opacity_logit) < min_opacity or the rows' largest
+ * scale (for children the reduced one) > prune_extent.  Writes count[n] (rows per Gaussian), action[n] (0 keep, 1 clone,
+ * 2 split) and offset[n+1], the exclusive prefix sum of count: offset[n] = the number of output rows, the one value
+ * the caller reads back.  A plan that could exceed int32 (n_gauss * max(n_split, 2) > INT32_MAX) is refused.
+ * ws: gcp_densify_plan_workspace_bytes(n_gauss) bytes.
+ *
+ * gcp_densify_fill: for every output row r in offset[i] .. offset[i+1]: src_row[r] = i, kind[r] = 0 survivor (moments
+ * carried) / 1 fresh copy / 2 split child.  A Gaussian's rows are contiguous, in Gaussian order; a split child's number
+ * is r - offset[src_row[r]].
+ *
+ * gcp_densify_rows: dst[r, :] = src[src_row[r], :] for rows of `width` floats (mode 0, parameters), or that where
+ * kind[r] == 0 and 0.0f elsewhere (mode 1, Adam moments).  Arrays 4-byte aligned; 16-byte accesses where width is a
+ * multiple of 4 and both arrays are 16-byte aligned.  A src_row outside [0, n_src_rows) gives a row of zeros.
+ *
+ * gcp_densify_split: for rows with kind == 2, parent p = src_row[r], child c = r - offset[p]:
+ *     mean_out[r] = mean[p] + R(q[p] / max(|q[p]|, 1e-8)) (sigma * z),  log_scale_out[r] = log(sigma / (0.8 n_split)),
+ * sigma = exp(log_scale[p]), R as uitility.py:231-254 (x, y, z, w).  z: Philox4x32-10, key (seed_lo, seed_hi), counter
+ * (p, c, 0, 0); outputs r0..r3 -> u_k = (r_k + 0.5) 2^-32 (ln u_k taken from 1 - u_k above 1/2, so the radius keeps float
+ * accuracy up to r_k = 2^32 - 1; the angle 2 pi u_k from the float32 u_k, absolute error 2e-7); z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0)
+ * sin(2 pi u1), z2 = sqrt(-2 ln u2) cos(2 pi u3).  Other rows are not touched.  mean / log_scale are the arrays BEFORE
+ * the pass (n_gauss rows), mean_out / log_scale_out those after it (n_rows rows). */
+int gcp_densify_accumulate(const float* grad_xy, const int64_t* index, int64_t m, float scale_x, float scale_y, float* norm_acc,
+                           int32_t* view_count, int64_t n_gauss, int32_t* n_bad, void* stream);
+size_t gcp_densify_plan_workspace_bytes(int64_t n_gauss);
+int gcp_densify_plan(const float* norm_acc, const int32_t* view_count, const float* log_scale, const float* opacity_logit,
+                     int64_t n_gauss, float grad_threshold, float dense_extent, float prune_extent, float min_opacity,
+                     int32_t n_split, int32_t* count, uint8_t* action, int32_t* offset, void* ws, size_t ws_bytes, void* stream);
+int gcp_densify_fill(const uint8_t* action, const int32_t* offset, int64_t n_gauss, int64_t n_rows, int32_t* src_row, uint8_t* kind,
+                     void* stream);
+int gcp_densify_rows(const float* src, int64_t n_src_rows, const int32_t* src_row, const uint8_t* kind, int64_t n_rows,
+                     int32_t width, int32_t mode, float* dst, void* stream);
+int gcp_densify_split(const float* mean, const float* quat_xyzw, const float* log_scale, const int32_t* src_row, const uint8_t* kind,
+                      const int32_t* offset, int64_t n_gauss, int64_t n_rows, int32_t n_split, uint32_t seed_lo, uint32_t seed_hi,
+                      float* mean_out, float* log_scale_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

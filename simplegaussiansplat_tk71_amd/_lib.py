@@ -122,6 +122,13 @@ SIGNATURES = {
     "gcp_splat_forward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 3 + [_i32] + [_c_void_p] * 5),
     "gcp_splat_gather": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
     "gcp_splat_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5 + [ctypes.c_float, _i32] + [_c_void_p] * 7),
+    # density control on the device (gcp_densify.hip): statistic, plan (count, action, offset), row list, row gather, split samples
+    "gcp_densify_accumulate": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, ctypes.c_float, ctypes.c_float, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "gcp_densify_plan_workspace_bytes": (_sz, [_i64]),
+    "gcp_densify_plan": (ctypes.c_int, [_c_void_p] * 4 + [_i64] + [ctypes.c_float] * 4 + [_i32] + [_c_void_p] * 4 + [_sz, _c_void_p]),
+    "gcp_densify_fill": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
+    "gcp_densify_rows": (ctypes.c_int, [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
+    "gcp_densify_split": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i64, _i32, ctypes.c_uint32, ctypes.c_uint32] + [_c_void_p] * 3),
 }
 
 ABI_VERSION = 4

@@ -38,6 +38,7 @@ from .cuda_kernel import custom_autograd_grouped_cumprod, render
 
 SH_FRAMES = {"camera": 0, "world": 1}
 CENTRES = ("pixel", "subpixel")
+DENSIFY_ON = ("position", "screen")
 
 
 def _splat_options(centres, cov_dilation, clamp_colour):
@@ -55,6 +56,7 @@ __all__ = [
     "GS_dataset",
     "GS_model_with_param",
     "HipAdam",
+    "accumulate_screen_grads",
     "camera_inputs",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
@@ -259,6 +261,34 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
     return cams, grad_iter, (width, height)
 
 
+def accumulate_screen_grads(grad_xy, index, scale, norm_acc, view_count, validate=False):
+    """The screen-space densification statistic of one camera (gcp_densify_accumulate, csrc/gcp_densify.hip), in place:
+    norm_acc[index[i]] += |grad_xy[i] * scale|, view_count[index[i]] += 1.  grad_xy float32 (m, 2): the loss's gradient with
+    respect to the splat centres in list order; index int64 (m,): the list's Gaussian ids, each at most once (what
+    `camera_inputs` returns as "index"); scale = (sx, sy); norm_acc float32 (N,), view_count int32 (N,).  GPU tensors only.
+    An id outside [0, N) is never written through; validate=True reads the number of such ids back first (one host read)
+    and raises, with nothing accumulated."""
+    if not (grad_xy.is_cuda and index.is_cuda and norm_acc.is_cuda and view_count.is_cuda):
+        raise RuntimeError("the densification statistic is a HIP kernel: tensors must live on the GPU (no CPU path)")
+    m, n = index.numel(), norm_acc.numel()
+    if index.dtype != torch.int64 or norm_acc.dtype != torch.float32 or view_count.dtype != torch.int32:
+        raise RuntimeError("accumulate_screen_grads expects int64 ids, a float32 norm and an int32 view count")
+    if tuple(grad_xy.shape) != (m, 2) or view_count.numel() != n or not (norm_acc.is_contiguous() and view_count.is_contiguous()):
+        raise RuntimeError("accumulate_screen_grads expects grad_xy (m, 2), index (m,) and contiguous norm_acc, view_count of one length")
+    grad_xy, index = grad_xy.detach().float().contiguous(), index.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(norm_acc.device):
+        stream = torch.cuda.current_stream(norm_acc.device).cuda_stream
+        if validate:
+            bad = torch.zeros(1, dtype=torch.int32, device=norm_acc.device)
+            _lib.check(lib.gcp_densify_accumulate(None, index.data_ptr(), m, 1.0, 1.0, None, None, n, bad.data_ptr(), stream),
+                       "gcp_densify_accumulate")
+            if int(bad):
+                raise RuntimeError(f"accumulate_screen_grads: {int(bad)} of {m} ids lie outside [0, {n})")
+        _lib.check(lib.gcp_densify_accumulate(grad_xy.data_ptr(), index.data_ptr(), m, float(scale[0]), float(scale[1]), norm_acc.data_ptr(),
+                                              view_count.data_ptr(), n, None, stream), "gcp_densify_accumulate")
+
+
 class HipAdam:
     """torch.optim.Adam's update (default betas / eps, no weight decay, no amsgrad — what the reference constructs at
     gs_model.py:43-47) on the HIP library: one streaming kernel per parameter tensor (csrc/gcp_optim.hip, gcp_adam_step)
@@ -329,11 +359,21 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
-                 active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False):
+                 active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position"):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
         the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
-        clamp_colour: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them."""
+        clamp_colour: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
+        densify_on: the statistic `densify_and_prune_device` decides on.  "position" (the default, the reference's): the norm
+        of the 3-D positional gradient per step, kept by `param_iter_update`.  "screen" (needs centres="subpixel"): the norm
+        of the loss's gradient with respect to the 2-D splat centre, per VIEW, scaled by (W/2, H/2) — the NDC unit other
+        3DGS trainers threshold in; `forward` and `render` collect it during `backward` in `screen_grads_norm` /
+        `screen_grads_views`.  `grad_threshold` has NOT been tuned for that statistic here: no full-length run on real poses
+        exists (the reference's checkout has no images.bin), the default is the reference's value for its own statistic."""
         super().__init__()
+        if densify_on not in DENSIFY_ON:
+            raise ValueError(f"densify_on: 'position' or 'screen', got {densify_on!r}")
+        if densify_on == "screen" and centres != "subpixel":
+            raise ValueError("densify_on='screen' needs centres='subpixel': with pixel centres the blend has no gradient w.r.t. the centre")
         if not 0 <= L_max <= 3:
             raise ValueError(f"L_max: 0..3, got {L_max}")
         if sh_frame not in SH_FRAMES:
@@ -361,6 +401,9 @@ class GS_model_with_param(torch.nn.Module):
         self.reference_layout = reference_layout
         self.mean_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
         self.mean_grads_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int16)
+        self.densify_on = densify_on
+        self.screen_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
+        self.screen_grads_views = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int32)
         self.changing_optimizer()
 
     # ---- optimiser plumbing (reference: gs_model.py:43-67) -------------------------------------------------
@@ -471,14 +514,138 @@ class GS_model_with_param(torch.nn.Module):
         self._replace(~prune)
         self.changing_optimizer()
 
-    def reset_opacity(self, reset_opacity):
-        """(:267-271)"""
+    def reset_opacity(self, reset_opacity, keep_optimizer=False):
+        """(:267-271).  keep_optimizer=True: the opacity is clamped in place and only its own two Adam moments are zeroed; every
+        other tensor's moments and every step count stay (the default rebuilds the optimiser, as the reference does)."""
         cap = torch.full_like(self.opacity.data, reset_opacity)
+        if keep_optimizer:
+            with torch.no_grad():
+                self.opacity.copy_(torch.logit(torch.minimum(torch.sigmoid(self.opacity.data), cap)))
+            state = self._optimizer.state.get(self.opacity)
+            if state:
+                state["exp_avg"].zero_()
+                state["exp_avg_sq"].zero_()
+            return
         self.opacity = torch.nn.Parameter(torch.logit(torch.minimum(torch.sigmoid(self.opacity.data), cap)))
         self.changing_optimizer()
 
+    # ---- density control on the device (csrc/gcp_densify.hip) -------------------------------------------------------
+    def _density_stats(self):
+        """The active statistic as the plan kernel reads it: (float32 norm, int32 count)."""
+        if self.densify_on == "screen":
+            return self.screen_grads_norm, self.screen_grads_views
+        return self.mean_grads_norm.float(), self.mean_grads_iter.to(torch.int32)
+
+    @torch.no_grad()
+    def densify_and_prune_device(self, extent, seed, n_split=2):
+        """Split, clone and prune in ONE pass of HIP kernels that keeps Adam's state; returns (n_before, n_after).
+
+        With g = statistic / max(count, 1) (see `densify_on`), s = the largest scale and hot = count > 0 and
+        g >= grad_threshold, every Gaussian takes one action, decided on the state before the call: split (hot,
+        s > percent_dense * extent: `n_split` children sampled from it, of scale s / (0.8 n_split), replace it), clone (hot
+        otherwise: the Gaussian and one copy) or keep; then the rows it would write are dropped if
+        sigmoid(opacity) < prunning_min_opacity or their largest scale > 0.1 * extent.  This is the clone -> split -> prune
+        sequence of other 3DGS trainers with zero statistics on new rows; `densify_and_prune` (the reference's order) lets
+        split children inherit the parent's statistic, so they may be cloned in the same call.
+        Rows come out in Gaussian order, a Gaussian's rows next to each other.  A surviving row keeps its exp_avg /
+        exp_avg_sq, fresh rows start at 0.0, every tensor's `step` is kept.  The split samples are Philox4x32-10 draws keyed
+        by `seed` (64 bits) and counted by (parent, child): the same on every rank, independent of torch's generators.  All
+        statistic arrays come back zeroed at the new length.  One 4-byte device->host read (the new row count).  GPU only."""
+        if not self.mean.is_cuda:
+            raise RuntimeError("density control on the device is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("densify_and_prune_device reads the new row count back: it cannot be captured into a graph")
+        names = ("mean", "variance_q", "variance_scale", "opacity", "color")
+        old = {k: getattr(self, k) for k in names}
+        src = {k: old[k].data.contiguous() for k in names}
+        dev, n = self.mean.device, self.mean.shape[0]
+        norm, views = (t.contiguous() for t in self._density_stats())
+        if norm.numel() != n or views.numel() != n:  # the active pair only: the other one is reallocated below
+            raise RuntimeError("the densification statistic does not have one row per Gaussian")
+        lib = _lib.load()
+        count, offset = (torch.empty(k, dtype=torch.int32, device=dev) for k in (n, n + 1))
+        action = torch.empty(n, dtype=torch.uint8, device=dev)
+        ws = torch.empty(lib.gcp_densify_plan_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        seed = int(seed) & (2 ** 64 - 1)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.gcp_densify_plan(norm.data_ptr(), views.data_ptr(), src["variance_scale"].data_ptr(), src["opacity"].data_ptr(), n,
+                                            float(self.grad_threshold), float(self.percent_dense * extent), float(0.1 * extent),
+                                            float(self.prunning_min_opacity), int(n_split), count.data_ptr(), action.data_ptr(),
+                                            offset.data_ptr(), ws.data_ptr(), ws.numel(), stream), "gcp_densify_plan")
+            m = int(offset[n])  # the one device->host read
+            src_row = torch.empty(m, dtype=torch.int32, device=dev)
+            kind = torch.empty(m, dtype=torch.uint8, device=dev)
+            _lib.check(lib.gcp_densify_fill(action.data_ptr(), offset.data_ptr(), n, m, src_row.data_ptr(), kind.data_ptr(), stream),
+                       "gcp_densify_fill")
+
+            def rows(t, mode):
+                out = torch.empty((m, *t.shape[1:]), dtype=torch.float32, device=dev)
+                _lib.check(lib.gcp_densify_rows(t.data_ptr(), n, src_row.data_ptr(), kind.data_ptr(), m, t[0].numel() if n else 0, mode,
+                                                out.data_ptr(), stream), "gcp_densify_rows")
+                return out
+
+            new = {k: rows(src[k], 0) for k in names}
+            _lib.check(lib.gcp_densify_split(src["mean"].data_ptr(), src["variance_q"].data_ptr(), src["variance_scale"].data_ptr(),
+                                             src_row.data_ptr(), kind.data_ptr(), offset.data_ptr(), n, m, int(n_split), seed & 0xFFFFFFFF,
+                                             seed >> 32, new["mean"].data_ptr(), new["variance_scale"].data_ptr(), stream),
+                       "gcp_densify_split")
+            state = {}
+            for k in names:
+                st = self._optimizer.state.get(old[k])
+                if st:
+                    state[k] = {"step": st["step"], "exp_avg": rows(st["exp_avg"].contiguous(), 1),
+                                "exp_avg_sq": rows(st["exp_avg_sq"].contiguous(), 1)}
+        for k in names:
+            setattr(self, k, torch.nn.Parameter(new[k]))
+        self.changing_optimizer()
+        for k, st in state.items():
+            self._optimizer.state[getattr(self, k)] = st
+        self.mean_grads_norm = torch.zeros(m, device=dev, dtype=torch.float32)
+        self.mean_grads_iter = torch.zeros(m, device=dev, dtype=torch.int16)
+        self.screen_grads_norm = torch.zeros(m, device=dev, dtype=torch.float32)
+        self.screen_grads_views = torch.zeros(m, device=dev, dtype=torch.int32)
+        return n, m
+
+    def allreduce_density_stats(self, group=None):
+        """Sum the screen-space statistic over the ranks, so that every rank takes the same densification decisions; under
+        backend "gloo" through the host, as `allreduce_grads`.  Under densify_on="position" there is nothing to sum: every rank
+        already holds the same statistic (the gradients were all-reduced before `param_iter_update`), and the call returns."""
+        import torch.distributed as dist
+
+        if self.densify_on != "screen":
+            return
+        for t in (self.screen_grads_norm, self.screen_grads_views):
+            if t.is_cuda and dist.get_backend(group) == "gloo":
+                host = t.cpu()
+                dist.all_reduce(host, group=group)
+                t.copy_(host)
+            else:
+                dist.all_reduce(t, group=group)
+
+    def _watch_centres(self, cams, width, height):
+        """densify_on="screen": hooks on the cameras' float centres that add the norm of their gradient, scaled to NDC units
+        (W/2, H/2), to `screen_grads_norm` and one view to `screen_grads_views` when `backward` reaches them."""
+        if self.densify_on != "screen" or not torch.is_grad_enabled():
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("densify_on='screen' collects its statistic in autograd hooks, which a captured graph (cuda_kernel.GraphedStep) "
+                               "does not replay: capture with densify_on='position'")
+        scale = (0.5 * width, 0.5 * height)
+        for cam in cams:
+            if cam is not None and cam["mean"].requires_grad:
+                cam["mean"].register_hook(lambda grad, index=cam["index"]: self._accumulate_centres(grad, index, scale))
+
+    def _accumulate_centres(self, grad, index, scale):
+        if self.screen_grads_norm.numel() != self.mean.shape[0]:
+            raise RuntimeError("screen_grads_norm does not have one row per Gaussian: with densify_on='screen' densify with "
+                               "densify_and_prune_device, which resizes it")
+        accumulate_screen_grads(grad, index, scale, self.screen_grads_norm, self.screen_grads_views)
+
     # ---- forward (:277-460) ------------------------------------------------------------------------------------
     def camera_inputs(self, P, K, wh, with_depth=False, capture_safe=False):
+        if capture_safe and self.densify_on == "screen":
+            raise RuntimeError("densify_on='screen' does not support capture-safe lists: its statistic is collected per kept list entry")
         return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
                              self.variance_pixel_tile_max_width, self.active_sh_degree, capture_safe=capture_safe,
                              with_depth=with_depth, sh_frame=self.sh_frame, centres=self.centres, cov_dilation=self.cov_dilation,
@@ -514,6 +681,7 @@ class GS_model_with_param(torch.nn.Module):
 
     def forward(self, P, K, wh, image_sample):
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh)
+        self._watch_centres(cams, width, height)
         images, names = [], []
         for cam, name in zip(cams, image_sample):
             if cam is None:
@@ -538,6 +706,7 @@ class GS_model_with_param(torch.nn.Module):
         maps after the same [1:, 1:] crop as `forward`; `names` are `image_sample`'s entries (default: camera indices) of the
         cameras that see anything — the others are dropped, as in `forward`."""
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
+        self._watch_centres(cams, width, height)
         names_in = list(range(P.shape[0])) if image_sample is None else image_sample
         images, depths, alphas, names = [], [], [], []
         for cam, name in zip(cams, names_in):

@@ -1,0 +1,414 @@
+"""Density control on the device (csrc/gcp_densify.hip, GS_model_with_param.densify_and_prune_device) on the GPU, against the
+torch / numpy formulation of tests/density_torch.py: the statistic, the plan and the row gather bit for bit, the split
+samples against float64 from the numpy Philox draws, Adam's state across the pass, the statistic through the model and
+the training loop."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from simplegaussiansplat_tk71_amd import _lib
+from simplegaussiansplat_tk71_amd import gs_model as gm
+from tests import density_torch as dt
+
+pytestmark = pytest.mark.gpu
+
+EXTENT = 10.0  # with percent_dense = 0.01 and the fixed 0.1: dense_extent 0.1, prune_extent 1.0 = dt.HYPER
+MODEL_HYPER = {"grad_threshold": 0.5, "percent_dense": 0.01, "prunning_min_opacity": 0.005}
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def device_plan(sc, device, n_split=2, hyper=dt.HYPER):
+    """gcp_densify_plan + gcp_densify_fill on the scene's statistic -> the dict of density_torch.plan, GPU tensors."""
+    lib = _lib.load()
+    n = sc["norm"].numel()
+    norm, views, log_scale, opacity = (sc[k].to(device).contiguous() for k in ("norm", "views", "variance_scale", "opacity"))
+    count, offset = torch.empty(n, dtype=torch.int32, device=device), torch.empty(n + 1, dtype=torch.int32, device=device)
+    action = torch.empty(n, dtype=torch.uint8, device=device)
+    ws = torch.empty(lib.gcp_densify_plan_workspace_bytes(n), dtype=torch.uint8, device=device)
+    _lib.check(lib.gcp_densify_plan(norm.data_ptr(), views.data_ptr(), log_scale.data_ptr(), opacity.data_ptr(), n, hyper["grad_threshold"],
+                                    hyper["dense_extent"], hyper["prune_extent"], hyper["min_opacity"], n_split, count.data_ptr(),
+                                    action.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel(), _stream(device)), "gcp_densify_plan")
+    m = int(offset[n])
+    src_row, kind = torch.empty(m, dtype=torch.int32, device=device), torch.empty(m, dtype=torch.uint8, device=device)
+    _lib.check(lib.gcp_densify_fill(action.data_ptr(), offset.data_ptr(), n, m, src_row.data_ptr(), kind.data_ptr(), _stream(device)),
+               "gcp_densify_fill")
+    return {"count": count, "action": action, "offset": offset, "M": m, "src_row": src_row, "kind": kind}
+
+
+def device_rows(src, pl, mode):
+    n, m = src.shape[0], pl["M"]
+    out = torch.full((m, *src.shape[1:]), float("nan"), device=src.device)
+    _lib.check(_lib.load().gcp_densify_rows(src.data_ptr(), n, pl["src_row"].data_ptr(), pl["kind"].data_ptr(), m, src[0].numel() if n else 0,
+                                            mode, out.data_ptr(), _stream(src.device)), "gcp_densify_rows")
+    return out
+
+
+def at_offset(t, words, device):
+    """`t` on the device in a view that starts `words` floats behind a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 4, device=device)
+    view = buf[words:words + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and (t.numel() == 0 or view.data_ptr() % 16 == 4 * words)  # an empty view has no address
+    return view
+
+
+def make_model(sc, device, **kw):
+    model = gm.GS_model_with_param(*(sc[k].clone().to(device) for k in dt.NAMES[:4]), L_max=math.isqrt(sc["color"].shape[1]) - 1,
+                                   **MODEL_HYPER, **kw)
+    with torch.no_grad():
+        model.color.copy_(sc["color"].to(device))
+    model.mean_grads_norm = sc["norm"].clone().to(device)
+    model.mean_grads_iter = sc["views"].to(torch.int16).to(device)
+    return model
+
+
+# ---- the statistic ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("m", [0, 1, 63, 64, 65, 257, 1000])
+def test_accumulate_equals_index_add(m, device):
+    n, scale = 1000, (32.0, 24.0)
+    g = torch.Generator().manual_seed(m)
+    index = torch.randperm(n, generator=g)[:m]
+    norm, views = torch.rand(n, generator=g), torch.randint(0, 5, (n,), generator=g).to(torch.int32)
+    got_norm, got_views = norm.to(device), views.to(device)
+    want_norm, want_views = norm.clone(), views.clone()
+    for _ in range(2):  # two calls accumulate
+        grad = torch.randn(m, 2, generator=g)
+        gm.accumulate_screen_grads(grad.to(device), index.to(device), scale, got_norm, got_views, validate=True)
+        want_norm.index_add_(0, index, (grad * torch.tensor(scale)).norm(dim=1))
+        want_views.index_add_(0, index, torch.ones(m, dtype=torch.int32))
+    torch.testing.assert_close(got_norm.cpu(), want_norm, rtol=1e-6, atol=0)
+    assert torch.equal(got_views.cpu(), want_views)
+
+
+@pytest.mark.parametrize("bad", [-1, 1000, 2 ** 40])
+def test_accumulate_refuses_an_id_out_of_range(bad, device):
+    n = 1000
+    index = torch.arange(65, device=device)
+    index[40] = bad
+    norm, views = torch.zeros(n, device=device), torch.zeros(n, dtype=torch.int32, device=device)
+    with pytest.raises(RuntimeError, match="outside"):
+        gm.accumulate_screen_grads(torch.ones(65, 2, device=device), index, (1.0, 1.0), norm, views, validate=True)
+    assert not norm.any() and not views.any()  # refused as a whole
+    # without the read-back the entry is skipped, never written through
+    gm.accumulate_screen_grads(torch.ones(65, 2, device=device), index, (1.0, 1.0), norm, views)
+    assert int(views.sum()) == 64 and int(views[40]) == 0 and not views[65:].any()
+
+
+# ---- plan and rows ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 2047, 2048, 2049, 4097, 70001])
+def test_plan_and_rows_equal_the_torch_formulation(n, device):
+    """Both sides of a block (256) and of the prefix sum's 2048-element chunk, and many chunks.  Every parameter row and every
+    carried moment bit-equal, fresh rows' moments exactly 0.0; sources at 0..3 floats behind a 16-byte boundary, so both the
+    16-byte path (widths 4, 12, 48 at offset 0) and the word path run; colour widths 1, 4, 9, 16 coefficients."""
+    sc = dt.scene(n, n_coeff=1)
+    want = dt.plan(sc["norm"], sc["views"], sc["variance_scale"], sc["opacity"], **dt.HYPER)
+    got = device_plan(sc, device)
+    assert got["M"] == want["M"]
+    for k in ("count", "action", "offset", "src_row", "kind"):
+        assert torch.equal(got[k].cpu(), want[k]), k
+    g = torch.Generator().manual_seed(n)
+    tensors = {k: sc[k] for k in dt.NAMES[:4]}
+    tensors.update({f"color{c}": torch.randn(n, c, 3, generator=g) for c in (1, 4, 9, 16)})
+    for name, t in tensors.items():
+        for words in range(4):
+            src = at_offset(t, words, device)
+            assert torch.equal(device_rows(src, got, 0).cpu(), dt.gather(want, t)), (name, words)
+            moments = device_rows(src, got, 1).cpu()
+            assert torch.equal(moments, dt.gather(want, t, moments=True)), (name, words)
+            assert not moments[want["kind"] != dt.SURVIVOR].any()
+
+
+def test_plan_is_the_same_for_another_number_of_children(device):
+    sc = dt.scene(2049)
+    for n_split in (1, 3):
+        want = dt.plan(sc["norm"], sc["views"], sc["variance_scale"], sc["opacity"], n_split=n_split, **dt.HYPER)
+        got = device_plan(sc, device, n_split=n_split)
+        for k in ("count", "action", "offset", "src_row", "kind"):
+            assert torch.equal(got[k].cpu(), want[k]), (n_split, k)
+
+
+def _state(model):
+    return {k: {s: (v.clone() if torch.is_tensor(v) else v) for s, v in model._optimizer.state[p].items()} for k, p in model.named_parameters()}
+
+
+def _five_steps(model, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    grads = {k: torch.randn(p.shape, generator=g).to(p.device) for k, p in model.named_parameters()}
+    for _ in range(5):
+        for k, p in model.named_parameters():
+            p.grad = grads[k].clone()
+        model.train_step()
+
+
+def test_all_pruned_leaves_zero_rows(device):
+    sc = dt.scene(300)
+    sc["opacity"][:] = -10.0
+    model = make_model(sc, device)
+    _five_steps(model)
+    assert model.densify_and_prune_device(EXTENT, seed=1) == (300, 0)
+    for k, p in model.named_parameters():
+        assert p.shape[0] == 0 and p.shape[1:] == sc[k].shape[1:], k
+        st = model._optimizer.state[p]
+        assert st["step"] == 5 and st["exp_avg"].shape == p.shape and st["exp_avg_sq"].shape == p.shape
+    for stat in (model.mean_grads_norm, model.mean_grads_iter, model.screen_grads_norm, model.screen_grads_views):
+        assert stat.shape == (0,)
+
+
+def test_nothing_hot_and_nothing_pruned_is_the_identity(device):
+    sc = dt.scene(2049)
+    sc["norm"][:] = 0.0
+    sc["opacity"][:] = 0.5
+    sc["variance_scale"][:] = math.log(0.05)
+    model = make_model(sc, device)
+    _five_steps(model)
+    before, state = {k: p.detach().clone() for k, p in model.named_parameters()}, _state(model)
+    assert model.densify_and_prune_device(EXTENT, seed=1) == (2049, 2049)
+    for k, p in model.named_parameters():
+        assert torch.equal(p.detach(), before[k]), k
+        st = model._optimizer.state[p]
+        assert st["step"] == state[k]["step"] == 5
+        assert torch.equal(st["exp_avg"], state[k]["exp_avg"]) and torch.equal(st["exp_avg_sq"], state[k]["exp_avg_sq"]), k
+
+
+# ---- split --------------------------------------------------------------------------------------------------------------
+def test_split_children_equal_the_float64_formulation(device):
+    """Child mean and log scale against float64 from the numpy Philox draws, within the project's absolute 1e-5 (DESIGN.md §4;
+    scene scale O(1)); the children of one parent differ; everything else of the pass equals the gather."""
+    for n_split, seed in ((2, 5), (3, 2 ** 40 + 17)):
+        sc = dt.scene(4097, n_coeff=4)
+        model = make_model(sc, device)
+        want = dt.plan(sc["norm"], sc["views"], sc["variance_scale"], sc["opacity"], n_split=n_split, **dt.HYPER)
+        assert model.densify_and_prune_device(EXTENT, seed=seed, n_split=n_split) == (4097, want["M"])
+        rows, mean, log_scale = dt.split_children(want, sc["mean"], sc["variance_q"], sc["variance_scale"], seed, n_split)
+        assert rows.numel() >= 8 * n_split
+        got_mean, got_scale = model.mean.detach().cpu(), model.variance_scale.detach().cpu()
+        err_mean = (got_mean[rows].double() - mean).abs().max().item()
+        err_scale = (got_scale[rows].double() - log_scale).abs().max().item()
+        print(f"n_split {n_split}: {rows.numel()} children, max |mean error| {err_mean:.3g}, max |log scale error| {err_scale:.3g}")
+        assert err_mean <= 1e-5 and err_scale <= 1e-5
+        family = got_mean[rows].reshape(-1, n_split, 3)  # a parent's children are contiguous
+        for a in range(n_split):
+            for b in range(a + 1, n_split):
+                assert bool((family[:, a] != family[:, b]).any(dim=1).all())
+        other = torch.ones(want["M"], dtype=torch.bool)
+        other[rows] = False
+        assert torch.equal(got_mean[other], dt.gather(want, sc["mean"])[other])
+        assert torch.equal(got_scale[other], dt.gather(want, sc["variance_scale"])[other])
+        for k in ("variance_q", "opacity", "color"):
+            assert torch.equal(getattr(model, k).detach().cpu(), dt.gather(want, sc[k])), k
+
+
+def test_split_samples_are_standard_normal(device):
+    """20 000 children of parents at the origin: z = diag(1 / sigma) R^T child is recovered without cancellation; per axis
+    |mean| <= 4 / sqrt(n) and |var - 1| <= 4 sqrt(2 / n) (four standard errors of n independent N(0, 1) draws)."""
+    n, g = 10000, torch.Generator().manual_seed(3)
+    sc = {"mean": torch.zeros(n, 3), "variance_q": torch.randn(n, 4, generator=g), "variance_scale": torch.log(0.2 + 0.4 * torch.rand(n, 3, generator=g)),
+          "opacity": torch.zeros(n, 1), "color": torch.zeros(n, 1, 3), "norm": torch.ones(n), "views": torch.ones(n, dtype=torch.int32)}
+    model = make_model(sc, device)
+    assert model.densify_and_prune_device(EXTENT, seed=11) == (n, 2 * n)  # every Gaussian splits, no child is pruned
+    child = model.mean.detach().cpu().double().reshape(n, 2, 3)
+    q = sc["variance_q"].double()
+    rot = dt.rotmat(q / q.norm(dim=1, keepdim=True))
+    z = torch.einsum("nji,ncj->nci", rot, child) / torch.exp(sc["variance_scale"].double())[:, None, :]
+    z = z.reshape(2 * n, 3)
+    want = torch.from_numpy(dt.split_normals(11, np.repeat(np.arange(n), 2), np.tile(np.arange(2), n)))
+    assert (z - want).abs().max().item() <= 1e-4  # recovered through float32 means: a plausibility check of the recovery itself
+    mean, var = z.mean(dim=0), z.var(dim=0)
+    print("mean", mean.tolist(), "var", var.tolist())
+    assert bool((mean.abs() <= 4 / math.sqrt(2 * n)).all()) and bool(((var - 1).abs() <= 4 * math.sqrt(2 / (2 * n))).all())
+
+
+def test_split_depends_on_the_seed_alone(device):
+    sc = dt.scene(4097)
+    out = []
+    for seed in (9, 9, 10):
+        model = make_model(sc, device)
+        model.densify_and_prune_device(EXTENT, seed=seed)
+        out.append({k: p.detach().clone() for k, p in model.named_parameters()})
+    for k in dt.NAMES:
+        assert torch.equal(out[0][k], out[1][k]), k  # the same seed twice: bit-identical
+        if k != "mean":
+            assert torch.equal(out[0][k], out[2][k]), k
+    want = dt.plan(sc["norm"], sc["views"], sc["variance_scale"], sc["opacity"], **dt.HYPER)
+    moved = (out[0]["mean"] != out[2]["mean"]).any(dim=1).cpu()
+    assert torch.equal(moved, want["kind"] == dt.CHILD)  # another seed moves every split child and nothing else
+
+
+# ---- Adam across the pass -----------------------------------------------------------------------------------------------
+def test_adam_state_survives_the_pass(device):
+    """`densify_and_prune` ends in a new optimiser with empty state; the device pass carries every survivor's moments and
+    every tensor's step count, and the next step is torch.optim.Adam's from the transplanted state (the bound of
+    test_hip_adam_equals_torch_adam: 1e-6 of the largest magnitude in each tensor)."""
+    sc = dt.scene(4097)
+    model = make_model(sc, device)
+    _five_steps(model)
+    state = _state(model)
+    lrs = {k: group["lr"] for group, (k, _) in zip(model._optimizer.param_groups, model.named_parameters())}
+    want = dt.plan(sc["norm"], sc["views"], sc["variance_scale"], sc["opacity"], **dt.HYPER)
+    assert model.densify_and_prune_device(EXTENT, seed=4) == (4097, want["M"])
+    survivor, src = (want["kind"] == dt.SURVIVOR).to(device), want["src_row"].long().to(device)
+    assert 8 <= int(survivor.sum()) < want["M"]
+    for k, p in model.named_parameters():
+        st = model._optimizer.state[p]
+        assert st["step"] == 5, k
+        for moment in ("exp_avg", "exp_avg_sq"):
+            assert torch.equal(st[moment][survivor], state[k][moment][src[survivor]]), (k, moment)
+            assert not st[moment][~survivor].any(), (k, moment)
+            assert torch.equal(st[moment].cpu(), dt.gather(want, state[k][moment].cpu(), moments=True)), (k, moment)
+    for stat in (model.mean_grads_norm, model.mean_grads_iter, model.screen_grads_norm, model.screen_grads_views):
+        assert stat.shape == (want["M"],) and not stat.any()
+    # one more step against torch.optim.Adam on the same rows with the state gathered by the torch formulation
+    theirs = {k: p.detach().clone().requires_grad_(True) for k, p in model.named_parameters()}
+    adam = torch.optim.Adam([{"params": [theirs[k]], "lr": lrs[k]} for k in dt.NAMES])
+    g = torch.Generator().manual_seed(1)
+    for k, p in model.named_parameters():
+        adam.state[theirs[k]] = {"step": torch.tensor(5.0), "exp_avg": dt.gather(want, state[k]["exp_avg"].cpu(), moments=True).to(device),
+                                 "exp_avg_sq": dt.gather(want, state[k]["exp_avg_sq"].cpu(), moments=True).to(device)}
+        grad = torch.randn(p.shape, generator=g).to(device)
+        p.grad, theirs[k].grad = grad.clone(), grad.clone()
+    model.train_step()
+    adam.step()
+    for k, p in model.named_parameters():
+        st = model._optimizer.state[p]
+        assert st["step"] == 6
+        for got, ref in ((p.detach(), theirs[k].detach()), (st["exp_avg"], adam.state[theirs[k]]["exp_avg"]),
+                         (st["exp_avg_sq"], adam.state[theirs[k]]["exp_avg_sq"])):
+            assert (got - ref).abs().max().item() <= 1e-6 * max(ref.abs().max().item(), 1e-30), k
+
+
+def test_reset_opacity_keeps_the_optimiser(device):
+    model = make_model(dt.scene(300), device)
+    _five_steps(model)
+    state, opt = _state(model), model._optimizer
+    model.reset_opacity(0.01, keep_optimizer=True)
+    assert model._optimizer is opt
+    assert float(torch.sigmoid(model.opacity.detach()).max()) <= 0.01 + 1e-6
+    for k, p in model.named_parameters():
+        st = opt.state[p]
+        assert st["step"] == 5
+        if k == "opacity":
+            assert not st["exp_avg"].any() and not st["exp_avg_sq"].any()
+        else:
+            assert torch.equal(st["exp_avg"], state[k]["exp_avg"]) and torch.equal(st["exp_avg_sq"], state[k]["exp_avg_sq"]), k
+    model.reset_opacity(0.005)  # the default: a new optimiser without state
+    assert model._optimizer is not opt and not model._optimizer.state
+
+
+# ---- the statistic through the model ------------------------------------------------------------------------------------
+def _small_world(device, n=300):
+    from examples.train_cameras import synthetic_scene
+
+    start, P, K, wh, targets = synthetic_scene(n, 2, 64, 48, 0, device)
+    q = torch.zeros(n, 4, device=device)
+    q[:, 3] = 1
+    args = (start.clone(), q, torch.full((n, 3), math.log(0.06), device=device), torch.zeros(n, 1, device=device))
+    return args, P, K, wh, targets
+
+
+def test_screen_statistic_through_the_model(device):
+    args, P, K, wh, targets = _small_world(device)
+    model = gm.GS_model_with_param(*args, centres="subpixel", densify_on="screen")
+    seen, inner = [], model.camera_inputs
+
+    def spy(*a, **kw):
+        out = inner(*a, **kw)
+        for cam in out[0]:
+            if cam["mean"].requires_grad:
+                cam["mean"].retain_grad()
+                seen.append(cam)
+        return out
+
+    model.camera_inputs = spy
+    n = model.mean.shape[0]
+    for step in (1, 2):
+        seen.clear()
+        images, kept, _ = model(P, K, wh, [0, 1])
+        assert kept == [0, 1]
+        gm.splat_loss(images, targets).backward()
+        want_norm, want_views = torch.zeros(n, device=device), torch.zeros(n, dtype=torch.int32, device=device)
+        for cam in seen:
+            assert cam["mean"].grad is not None and cam["mean"].grad.abs().sum() > 0
+            want_norm.index_add_(0, cam["index"], (cam["mean"].grad * torch.tensor([32.0, 24.0], device=device)).norm(dim=1))
+            want_views.index_add_(0, cam["index"], torch.ones_like(cam["index"], dtype=torch.int32))
+        if step == 1:
+            torch.testing.assert_close(model.screen_grads_norm, want_norm, rtol=1e-6, atol=0)
+            assert torch.equal(model.screen_grads_views, want_views)
+            assert int(want_views.max()) == 2  # views count per camera, not per step
+            first = model.screen_grads_norm.clone()
+        else:  # the second step accumulates on the first
+            torch.testing.assert_close(model.screen_grads_norm, first + want_norm, rtol=1e-6, atol=0)
+            assert torch.equal(model.screen_grads_views, 2 * want_views)
+        model._optimizer.zero_grad()
+    # nothing is collected without gradients, under "position", or for capture-safe lists
+    with torch.no_grad():
+        model(P, K, wh, [0, 1])
+    assert torch.equal(model.screen_grads_views, 2 * want_views)
+    with pytest.raises(RuntimeError, match="capture-safe"):
+        inner(P, K, wh.tolist(), capture_safe=True)
+    plain = gm.GS_model_with_param(*args, centres="subpixel")
+    gm.splat_loss(plain(P, K, wh, [0, 1])[0], targets).backward()
+    assert not plain.screen_grads_norm.any() and not plain.screen_grads_views.any()
+    # the statistic is the one the device pass decides on, and it comes back zeroed at the new length
+    n_before, n_after = model.densify_and_prune_device(1.0, seed=0)
+    assert n_before == n and model.screen_grads_norm.shape == (n_after,) and not model.screen_grads_views.any()
+
+
+# ---- the loop -----------------------------------------------------------------------------------------------------------
+def test_training_loop_with_device_density_control(device):
+    from examples.train_cameras import synthetic_scene, train
+
+    start, P, K, wh, targets = synthetic_scene(600, 6, 64, 48, 0, device)
+    model, losses = train(start, P, K, wh, targets, iterations=150, densify_from_iter=60, densification_interval=45,
+                          opacity_reset_interval=0, log=lambda *_: None, centres="subpixel", densify="device", densify_on="screen")
+    first, last, n = np.mean(losses[:10]), np.mean(losses[-10:]), model.mean.shape[0]
+    print(f"loss {first:.5f} -> {last:.5f}, Gaussians 600 -> {n}")
+    assert all(l == l for l in losses)
+    assert last < first
+    assert n != 600
+    for t in (model.variance_q, model.color, model.screen_grads_norm, model.screen_grads_views, model.mean_grads_iter):
+        assert t.shape[0] == n
+    assert all(st["step"] == 150 for st in model._optimizer.state.values())  # Adam was never restarted
+
+
+def test_default_loop_makes_the_calls_it_made_before(device, monkeypatch):
+    """With the defaults `train` computes what it computed before the device path existed: its 30 losses and its final
+    number of Gaussians equal, bit for bit, those the commit before this feature produced on an MI355X (recorded in
+    tests/golden/default_loop_losses.json; the gradients and torch's generators are bit-reproducible run to run, which the
+    second run here shows again).  And the loop's calls into the model are the earlier ones: the reference's
+    densify_and_prune and the one-argument reset_opacity, never the device pass, the statistic's all-reduce or a hook on
+    the centres."""
+    import json
+    import os
+
+    from examples.train_cameras import synthetic_scene, train
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "default_loop_losses.json")) as f:
+        want = json.load(f)
+    calls = []
+
+    def record(name):
+        inner = getattr(gm.GS_model_with_param, name)
+
+        def wrapped(self, *a, **kw):
+            calls.append((name, len(a), tuple(sorted(kw))))
+            return inner(self, *a, **kw)
+
+        monkeypatch.setattr(gm.GS_model_with_param, name, wrapped)
+
+    for name in ("densify_and_prune", "densify_and_prune_device", "reset_opacity", "allreduce_density_stats", "_accumulate_centres"):
+        record(name)
+    start, P, K, wh, targets = synthetic_scene(600, 6, 64, 48, 0, device)
+    for _ in range(2):
+        calls.clear()
+        model, losses = train(start, P, K, wh, targets, iterations=30, densify_from_iter=10, densification_interval=10,
+                              opacity_reset_interval=20, log=lambda *_: None)
+        assert calls == [("densify_and_prune", 1, ()), ("densify_and_prune", 1, ()), ("reset_opacity", 1, ()),
+                         ("densify_and_prune", 1, ())], calls
+        assert model.densify_on == "position" and not model._optimizer.state  # rebuilt, empty: the reference's behaviour
+        assert len(losses) == 30 and losses == want["losses"], [(k, a, b) for k, (a, b) in enumerate(zip(losses, want["losses"])) if a != b][:3]
+        assert model.mean.shape[0] == want["gaussians"]
