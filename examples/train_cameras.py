@@ -15,6 +15,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --centres subpixel --dilation 0.3 --clamp-colour
                                                              # float splat centres at px + 0.5 (their gradient trains the
                                                              # positions), 0.3 px^2 covariance dilation, colour clamped at 0
+    python examples/train_cameras.py --centres subpixel --dilation 0.3 --antialias
+                                                             # the same dilation with its opacity compensation: a Gaussian
+                                                             # keeps the energy it had before the dilation (Mip-Splatting's 2-D filter)
     python examples/train_cameras.py --centres subpixel --densify device --densify-on screen
                                                              # split / clone / prune in one pass of HIP kernels that keeps Adam's
                                                              # moments, decided on the screen-space gradient of the centres
@@ -79,7 +82,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           densify_from_iter=500, densify_until_iter=15000, densification_interval=100, opacity_reset_interval=3000,
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
-          densify="reference", densify_on="position"):
+          densify="reference", densify_on="position", antialias=False):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -88,7 +91,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `sh_degree` (0..3) and `sh_frame` ("camera" / "world"): the appearance model (gs_model.camera_inputs); `sh_every` N > 0:
     start at degree 0 and activate one more every N iterations.  `load_ply`: start from that scene file instead of `start`
     (its degree replaces `sh_degree`); `save_ply`: write the trained scene there (rank 0).
-    `centres`, `dilation`, `clamp_colour`: the projection's `centres`, `cov_dilation`, `clamp_colour` (gs_model.camera_inputs).
+    `centres`, `dilation`, `clamp_colour`, `antialias`: the projection's `centres`, `cov_dilation`, `clamp_colour`, `antialias`
+    (gs_model.camera_inputs); `antialias` needs a `dilation` > 0.
     `densify`: "reference" (the default: `densify_and_prune` / `reset_opacity`, which rebuild Adam without its moments, split
     samples from torch's generator) or "device" (`densify_and_prune_device` with seed + iteration and
     `reset_opacity(keep_optimizer=True)`: one pass of HIP kernels, Adam's state kept, the statistic summed over the ranks
@@ -106,6 +110,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     opacity = torch.full((n, 1), math.log(opacity_init / (1 - opacity_init)), device=dev)
     sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None, "centres": centres, "cov_dilation": dilation,
           "clamp_colour": clamp_colour}
+    if antialias:
+        sh["antialias"] = antialias
     if densify_on != "position":
         sh["densify_on"] = densify_on
     if load_ply is not None:
@@ -199,11 +205,15 @@ if __name__ == "__main__":
     ap.add_argument("--dilation", type=float, default=None, metavar="F",
                     help="added to the diagonal of the pixel covariance (0.3: other 3DGS renderers'; default 1e-6)")
     ap.add_argument("--clamp-colour", action="store_true", help="clamp the SH colour at 0")
+    ap.add_argument("--antialias", action="store_true",
+                    help="scale each opacity by sqrt(det Sigma / det Sigma'), the energy the dilation adds (needs --dilation > 0)")
     ap.add_argument("--densify", choices=("reference", "device"), default="reference",
                     help="device = split / clone / prune in one pass of HIP kernels that keeps Adam's moments; reference = the reference's")
     ap.add_argument("--densify-on", choices=("position", "screen"), default="position",
                     help="statistic of --densify device: screen = gradient of the 2-D centres per view (needs --centres subpixel)")
     a = ap.parse_args()
+    if a.antialias and not (a.dilation is not None and a.dilation > 0):
+        ap.error("--antialias requires --dilation F with F > 0")
     background = a.background if a.background in (None, "random") else tuple(float(v) for v in a.background.split(","))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)) % max(1, torch.cuda.device_count()))
@@ -223,7 +233,8 @@ if __name__ == "__main__":
     _, losses = train(start, P, K, wh, targets, iterations=a.iterations, densify_from_iter=a.densify_from, rank=rank, world=world,
                       log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas, sh_degree=a.sh_degree,
                       sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply, centres=a.centres,
-                      dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on)
+                      dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on,
+                      antialias=a.antialias)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

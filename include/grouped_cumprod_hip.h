@@ -607,7 +607,24 @@ int gcp_project_backward_sh(const float* mean, const float* quat_xyzw, const flo
  * Every entry point returns GCP_ERR_INVALID_ARGUMENT, before any HIP call, for sh_degree / n_basis / sh_frame out of range
  * (as gcp_project_forward_sh), cov_eps negative or not finite, mean_offset not finite, clamp_colour outside {0, 1}, a NULL
  * array with Gaussians to process, or a misaligned record / vinv / mean_xy; n_gauss == 0 (n_kept == 0) is a no-op after
- * the checks of the scalar arguments. */
+ * the checks of the scalar arguments.
+ *
+ * gcp_splat_forward_flags / gcp_splat_backward_flags: the same calls with `int32_t flags` where clamp_colour stands, a set
+ * of GCP_SPLAT_* bits; any other bit is refused with GCP_ERR_INVALID_ARGUMENT before any HIP call.  gcp_splat_forward and
+ * gcp_splat_backward are these with flags = clamp_colour (still refusing a clamp_colour outside {0, 1}).
+ *   GCP_SPLAT_CLAMP_COLOUR: clamp_colour = 1.
+ *   GCP_SPLAT_ANTIALIAS: opacity compensation of the dilation.  Sigma' = Sigma + cov_eps I paints sqrt(det Sigma' / det Sigma)
+ *     times the energy of the Gaussian it replaces; with this bit the record's opacity word (the gather's alpha) holds
+ *     sigmoid(o) rho,  rho = sqrt(max(det0, 0) / det),  det0 = a0 d0 - b c  on the clamped pixel covariance BEFORE cov_eps,
+ *     det = (a0 + cov_eps)(d0 + cov_eps) - b c + 1e-6, the determinant Sigma'^-1 is formed with.  Every other word of the
+ *     record, sort_key, keep and row_of are what they are without the bit.  Backward: grad_alpha is dL/d(sigmoid(o) rho);
+ *     grad_opacity_logit = grad_alpha rho s (1 - s) with s = sigmoid(o), and dL/drho = grad_alpha s is added to the
+ *     covariance's gradient through both determinants, (rho / 2)(adj(Sigma)^T / det0 - adj(Sigma')^T / det), under the
+ *     rule of the clamped entries.  A Gaussian with det0 <= 0 (a covariance that underflowed or lost its rank to rounding)
+ *     has rho = 0: its opacity is exactly 0, its logit gets 0, and nothing passes through rho.  Without a dilation
+ *     (cov_eps = 1e-6) rho is 1 up to the two 1e-6: the bit is meant for cov_eps > 0 such as 0.3. */
+#define GCP_SPLAT_CLAMP_COLOUR 1
+#define GCP_SPLAT_ANTIALIAS 2
 int gcp_splat_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
                       const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
                       int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
@@ -622,6 +639,18 @@ int gcp_splat_backward(const float* mean, const float* quat_xyzw, const float* l
                        const float* grad_l_d, const float* grad_depth /* may be NULL */, float cov_eps, int32_t clamp_colour,
                        const float* grad_mean_xy /* may be NULL */, float* grad_mean, float* grad_quat, float* grad_log_scale,
                        float* grad_opacity_logit, float* grad_sh_coeff, void* stream);
+int gcp_splat_forward_flags(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                            const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                            int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
+                            float mean_offset, int32_t flags, float* record, int32_t* sort_key, uint8_t* keep, int32_t* row_of,
+                            void* stream);
+int gcp_splat_backward_flags(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                             const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                             int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv,
+                             const float* grad_alpha, const float* grad_l_d, const float* grad_depth /* may be NULL */,
+                             float cov_eps, int32_t flags, const float* grad_mean_xy /* may be NULL */, float* grad_mean,
+                             float* grad_quat, float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff,
+                             void* stream);
 
 /* ---- the caller's training loss, fused ---------------------------------------------------
  * (1 - lambda) * mean|a - b| + lambda * (1 - mean SSIM(a, b)) of gs_control.py:180-182 (kornia.metrics.ssim with an

@@ -122,6 +122,9 @@ SIGNATURES = {
     "gcp_splat_forward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 3 + [_i32] + [_c_void_p] * 5),
     "gcp_splat_gather": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
     "gcp_splat_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5 + [ctypes.c_float, _i32] + [_c_void_p] * 7),
+    # the same two with a set of GCP_SPLAT_* flags (SPLAT_CLAMP_COLOUR, SPLAT_ANTIALIAS below) where clamp_colour stands
+    "gcp_splat_forward_flags": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 3 + [_i32] + [_c_void_p] * 5),
+    "gcp_splat_backward_flags": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32] + [_c_void_p] * 5 + [ctypes.c_float, _i32] + [_c_void_p] * 7),
     # density control on the device (gcp_densify.hip): statistic, plan (count, action, offset), row list, row gather, split samples
     "gcp_densify_accumulate": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, ctypes.c_float, ctypes.c_float, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p]),
     "gcp_densify_plan_workspace_bytes": (_sz, [_i64]),
@@ -132,6 +135,7 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 4
+SPLAT_CLAMP_COLOUR, SPLAT_ANTIALIAS = 1, 2  # GCP_SPLAT_* of the header
 
 _lib = None
 

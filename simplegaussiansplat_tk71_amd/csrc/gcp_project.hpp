@@ -56,6 +56,28 @@ struct Projected {
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
+// Opacity compensation of the dilation (gcp_splat.hip, `antialias`): Sigma' = Sigma + cov_eps I spreads a Gaussian over more
+// pixels than Sigma does, so its opacity is scaled by rho = sqrt(det Sigma / det Sigma') and the energy it paints,
+// 2 pi alpha rho sqrt(det Sigma'), is that of the Gaussian before the dilation.  det0 = a0 d0 - b c on the clamped entries
+// before cov_eps; the denominator is p.det, 1e-6 included: the determinant Sigma'^-1 = adj / det is formed with.
+// det0 <= 0 (a covariance that underflowed, or lost its rank to rounding): rho = 0, and nothing passes through it.
+struct Compensation {
+  float a0, d0;     // clamped diagonal before cov_eps
+  float rho;        // sqrt(max(det0, 0) / det)
+  float rho_det0;   // rho / det0 = 1 / (sqrt(det0) sqrt(det)), finite for every positive det0; 0 where det0 <= 0
+};
+
+__device__ __forceinline__ Compensation compensation(const Projected& p) {
+  const float lim = 3.4028234663852886e+38f / 1000.f;
+  Compensation k;
+  k.a0 = clampf(p.cov[0], -lim, lim);
+  k.d0 = clampf(p.cov[3], -lim, lim);
+  const float det0 = k.a0 * k.d0 - p.b * p.c;
+  k.rho = sqrtf(fmaxf(det0, 0.f) / p.det);
+  k.rho_det0 = det0 > 0.f ? 1.f / (sqrtf(det0) * sqrtf(p.det)) : 0.f;
+  return k;
+}
+
 // The direction the SH basis is evaluated on.  Camera frame: `view` itself.  World frame: W = P[:, :3] is orthonormal and
 // t = W (m - c), so the unit vector from the camera centre c to the Gaussian is W^T t / |t| = -W^T view.
 template <bool WORLD>
@@ -221,14 +243,15 @@ __device__ __forceinline__ float sh_colour(const float* sh, int ch, int sh_degre
 // MAXDEG: the highest SH degree the instantiation can evaluate (sh_degree <= MAXDEG is the caller's to ensure).
 // SPLAT (gcp_splat.hip; false: cov_eps, mean_offset and clamp_colour are not read): the centre stays a float, stored as
 // px + mean_offset, and the box goes around it, ceil(c - h) .. floor(c + h); cov_eps replaces the 1e-6 on the covariance's
-// diagonal; clamp_colour: l = max(SH sum, 0) per channel.
+// diagonal; clamp_colour: l = max(SH sum, 0) per channel; antialias: the opacity word holds sigmoid(o) rho (`compensation`),
+// every other word is what it is without it.
 template <int MAXDEG, bool WORLD, bool SPLAT>
 __device__ __forceinline__ void project_fwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
     const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp, float cov_eps,
     float mean_offset, bool clamp_colour, float4* __restrict__ record, int* __restrict__ sort_key, uint8_t* __restrict__ keep,
-    int* __restrict__ row_of) {
+    int* __restrict__ row_of, bool antialias = false) {
   extern __shared__ float s_stage[];
   const ParamTile tile = param_tile(s_stage, n_basis);
   const Camera cam = load_camera(cam_P, cam_K);
@@ -279,7 +302,9 @@ __device__ __forceinline__ void project_fwd(
       if constexpr (SPLAT)
         if (clamp_colour && l[ch] < 0.f) l[ch] = 0.f;  // the test the backward repeats on the same sum
     }
-    const float alpha = 1.f / (1.f + expf(-opacity[i]));
+    float alpha = 1.f / (1.f + expf(-opacity[i]));
+    if constexpr (SPLAT)
+      if (antialias) alpha *= compensation(p).rho;
     float4* rec = record + 4 * i;
     rec[0] = make_float4(__int_as_float(x0), __int_as_float(y0), __int_as_float(x1), __int_as_float(y1));
     rec[1] = make_float4(centre[0], centre[1], p.d / p.det, -p.b / p.det);
@@ -326,7 +351,9 @@ __device__ __forceinline__ void project_gather(
 // SPLAT (gcp_splat.hip; false leaves the chain of gcp_project.hip as it is): cov_eps replaces the 1e-6 on the covariance's
 // diagonal; g_depth is tested at run time instead of DEPTH; g_mean_xy (may be NULL) is dL/d(float pixel centre) in list
 // order, chained through px = ph0 / pz, py = ph1 / pz, ph = K t, pz = max(ph2, 1e-2) into dL/dt (zero where the centre was
-// clamped at +-ilim); clamp_colour: a channel whose SH sum is < 0 was clamped to 0 by the forward and passes no gradient.
+// clamped at +-ilim); clamp_colour: a channel whose SH sum is < 0 was clamped to 0 by the forward and passes no gradient;
+// antialias: g_alpha is dL/d(sigmoid(o) rho) — the logit gets g_alpha rho s (1 - s), and dL/drho = g_alpha s reaches the
+// covariance through both determinants of rho = sqrt(det0 / det), added to dL/dA before the clamped entries are zeroed.
 template <int MAXDEG, bool WORLD, bool DEPTH, bool SPLAT = false>
 __device__ __forceinline__ void project_bwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
@@ -335,7 +362,7 @@ __device__ __forceinline__ void project_bwd(
     const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
     const float* __restrict__ g_depth, float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale,
     float* __restrict__ grad_opacity, float* __restrict__ grad_color, float cov_eps = 1e-6f, bool clamp_colour = false,
-    const float* __restrict__ g_mean_xy = nullptr) {
+    const float* __restrict__ g_mean_xy = nullptr, bool antialias = false) {
   // parameter rows come in and gradient rows go out through LDS as contiguous runs: straight from / to registers they are
   // 37 + 38 four-byte accesses per thread, 12-108 bytes apart (gradient rows direct: 365 us per 10^6 Gaussians; staged: 140)
   extern __shared__ float s_stage[];
@@ -366,7 +393,7 @@ __device__ __forceinline__ void project_bwd(
 
     // opacity = sigmoid(o)
     const float al = 1.f / (1.f + expf(-opacity[i]));
-    grad_opacity[i] = g_alpha[r] * al * (1.f - al);
+    if (!(SPLAT && antialias)) grad_opacity[i] = g_alpha[r] * al * (1.f - al);  // antialias: below, where rho is formed
 
     // colour: l_d[ch] = sum_k B_k(dir) sh[k][ch]
     constexpr int NB = (MAXDEG + 1) * (MAXDEG + 1);
@@ -441,6 +468,18 @@ __device__ __forceinline__ void project_bwd(
     const float gdet = -(sdot / p.det) / p.det;  // not sdot / det^2: a clamped covariance entry takes det past sqrt(FLT_MAX)
     const float lim = 3.4028234663852886e+38f / 1000.f;
     float D[4] = {g11 / p.det + gdet * p.d, -g01 / p.det - gdet * p.c, -g10 / p.det - gdet * p.b, g00 / p.det + gdet * p.a};
+    if constexpr (SPLAT) {
+      if (antialias) {  // opacity = sigmoid(o) rho;  d rho / dA = (rho / 2) (adj(A0)^T / det0 - adj(A)^T / det)
+        const Compensation comp = compensation(p);  // formed here, not next to `al`: nothing of it lives through the colour chain
+        const float s = 1.f / (1.f + expf(-opacity[i])), gs = g_alpha[r] * s;
+        grad_opacity[i] = (g_alpha[r] * comp.rho) * (s * (1.f - s));
+        const float h = 0.5f * gs, over_det = comp.rho / p.det;
+        D[0] += h * (comp.d0 * comp.rho_det0 - p.d * over_det);
+        D[1] += h * (p.c * over_det - p.c * comp.rho_det0);
+        D[2] += h * (p.b * over_det - p.b * comp.rho_det0);
+        D[3] += h * (comp.a0 * comp.rho_det0 - p.a * over_det);
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (!(fabsf(p.cov[k]) <= lim)) D[k] = 0.f;  // clamped (or NaN): no gradient

@@ -31,10 +31,11 @@ __global__ __launch_bounds__(kThreads) void k_splat_fwd(
     const float* __restrict__ mean, const float* __restrict__ q, const float* __restrict__ log_scale,
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
     const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, int width, int height, float box_clamp, float cov_eps,
-    float mean_offset, int clamp_colour, float4* __restrict__ record, int* __restrict__ sort_key, uint8_t* __restrict__ keep,
+    float mean_offset, int flags, float4* __restrict__ record, int* __restrict__ sort_key, uint8_t* __restrict__ keep,
     int* __restrict__ row_of) {
   project_fwd<MAXDEG, WORLD, true>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, width, height, box_clamp,
-                                   cov_eps, mean_offset, clamp_colour != 0, record, sort_key, keep, row_of);
+                                   cov_eps, mean_offset, (flags & GCP_SPLAT_CLAMP_COLOUR) != 0, record, sort_key, keep, row_of,
+                                   (flags & GCP_SPLAT_ANTIALIAS) != 0);
 }
 
 // project_gather with the centre as two floats; `depth` may be NULL
@@ -54,29 +55,29 @@ __global__ __launch_bounds__(kThreads) void k_splat_bwd(
     const float* __restrict__ opacity, const float* __restrict__ color, const float* __restrict__ cam_P,
     const float* __restrict__ cam_K, i64 n, int sh_degree, int n_basis, const int* __restrict__ row_of,
     const float* __restrict__ g_vinv, const float* __restrict__ g_alpha, const float* __restrict__ g_ld,
-    const float* __restrict__ g_depth, float cov_eps, int clamp_colour, const float* __restrict__ g_mean_xy,
+    const float* __restrict__ g_depth, float cov_eps, int flags, const float* __restrict__ g_mean_xy,
     float* __restrict__ grad_mean, float* __restrict__ grad_q, float* __restrict__ grad_log_scale, float* __restrict__ grad_opacity,
     float* __restrict__ grad_color) {
   project_bwd<MAXDEG, WORLD, false, true>(mean, q, log_scale, opacity, color, cam_P, cam_K, n, sh_degree, n_basis, row_of, g_vinv,
                                           g_alpha, g_ld, g_depth, grad_mean, grad_q, grad_log_scale, grad_opacity, grad_color, cov_eps,
-                                          clamp_colour != 0, g_mean_xy);
+                                          (flags & GCP_SPLAT_CLAMP_COLOUR) != 0, g_mean_xy, (flags & GCP_SPLAT_ANTIALIAS) != 0);
 }
 
-bool splat_arguments_valid(float cov_eps, int32_t clamp_colour) {
-  return std::isfinite(cov_eps) && cov_eps >= 0.f && (clamp_colour == 0 || clamp_colour == 1);
+bool splat_arguments_valid(float cov_eps, int32_t flags) {
+  return std::isfinite(cov_eps) && cov_eps >= 0.f && (flags & ~(GCP_SPLAT_CLAMP_COLOUR | GCP_SPLAT_ANTIALIAS)) == 0;
 }
 
 }  // namespace
 
 extern "C" {
 
-int gcp_splat_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
-                      const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
-                      int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
-                      float mean_offset, int32_t clamp_colour, float* record, int32_t* sort_key, uint8_t* keep, int32_t* row_of,
-                      void* stream) {
+int gcp_splat_forward_flags(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                            const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                            int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
+                            float mean_offset, int32_t flags, float* record, int32_t* sort_key, uint8_t* keep, int32_t* row_of,
+                            void* stream) {
   const int rc = check_projection_call(
-      n_gauss <= 0x7fffffff && width >= 0 && height >= 0 && splat_arguments_valid(cov_eps, clamp_colour) && std::isfinite(mean_offset),
+      n_gauss <= 0x7fffffff && width >= 0 && height >= 0 && splat_arguments_valid(cov_eps, flags) && std::isfinite(mean_offset),
       {mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K}, n_gauss, sh_degree, n_basis, sh_frame,
       {record, sort_key, keep, row_of});
   if (rc != kLaunch) return rc;
@@ -85,9 +86,20 @@ int gcp_splat_forward(const float* mean, const float* quat_xyzw, const float* lo
   auto kernel = pick_kernel(sh_degree, sh_frame, k_splat_fwd<2, false>, k_splat_fwd<2, true>, k_splat_fwd<3, false>, k_splat_fwd<3, true>);
   hipLaunchKernelGGL(kernel, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
                      opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, (int)width, (int)height,
-                     box_clamp, cov_eps, mean_offset, (int)clamp_colour, (float4*)record, sort_key, keep, row_of);
+                     box_clamp, cov_eps, mean_offset, (int)flags, (float4*)record, sort_key, keep, row_of);
   GCP_HIP(hipGetLastError());
   return GCP_OK;
+}
+
+int gcp_splat_forward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                      const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                      int32_t n_basis, int32_t sh_frame, int32_t width, int32_t height, float box_clamp, float cov_eps,
+                      float mean_offset, int32_t clamp_colour, float* record, int32_t* sort_key, uint8_t* keep, int32_t* row_of,
+                      void* stream) {
+  if (clamp_colour != 0 && clamp_colour != 1) return GCP_ERR_INVALID_ARGUMENT;  // a switch here, not a set of flags
+  return gcp_splat_forward_flags(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, sh_frame,
+                                 width, height, box_clamp, cov_eps, mean_offset, clamp_colour ? GCP_SPLAT_CLAMP_COLOUR : 0, record,
+                                 sort_key, keep, row_of, stream);
 }
 
 int gcp_splat_gather(const float* record, const int32_t* perm, int64_t n_kept, int32_t* start_xy, int32_t* end_xy, float* mean_xy,
@@ -105,14 +117,14 @@ int gcp_splat_gather(const float* record, const int32_t* perm, int64_t n_kept, i
   return GCP_OK;
 }
 
-int gcp_splat_backward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
-                       const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
-                       int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
-                       const float* grad_l_d, const float* grad_depth, float cov_eps, int32_t clamp_colour, const float* grad_mean_xy,
-                       float* grad_mean, float* grad_quat, float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff,
-                       void* stream) {
+int gcp_splat_backward_flags(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                             const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                             int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv,
+                             const float* grad_alpha, const float* grad_l_d, const float* grad_depth, float cov_eps, int32_t flags,
+                             const float* grad_mean_xy, float* grad_mean, float* grad_quat, float* grad_log_scale,
+                             float* grad_opacity_logit, float* grad_sh_coeff, void* stream) {
   // the upstream arrays may be NULL when no Gaussian was kept
-  const int rc = check_projection_call(splat_arguments_valid(cov_eps, clamp_colour), {mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K},
+  const int rc = check_projection_call(splat_arguments_valid(cov_eps, flags), {mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K},
                                        n_gauss, sh_degree, n_basis, sh_frame,
                                        {row_of, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff});
   if (rc != kLaunch) return rc;
@@ -120,10 +132,22 @@ int gcp_splat_backward(const float* mean, const float* quat_xyzw, const float* l
   auto kernel = pick_kernel(sh_degree, sh_frame, k_splat_bwd<2, false>, k_splat_bwd<2, true>, k_splat_bwd<3, false>, k_splat_bwd<3, true>);
   hipLaunchKernelGGL(kernel, dim3(grid_for(n_gauss)), dim3(kThreads), lds, (hipStream_t)stream, mean, quat_xyzw, log_scale,
                      opacity_logit, sh_coeff, cam_P, cam_K, (i64)n_gauss, (int)sh_degree, (int)n_basis, row_of, grad_vinv, grad_alpha,
-                     grad_l_d, grad_depth, cov_eps, (int)clamp_colour, grad_mean_xy, grad_mean, grad_quat, grad_log_scale,
+                     grad_l_d, grad_depth, cov_eps, (int)flags, grad_mean_xy, grad_mean, grad_quat, grad_log_scale,
                      grad_opacity_logit, grad_sh_coeff);
   GCP_HIP(hipGetLastError());
   return GCP_OK;
+}
+
+int gcp_splat_backward(const float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit,
+                       const float* sh_coeff, const float* cam_P, const float* cam_K, int64_t n_gauss, int32_t sh_degree,
+                       int32_t n_basis, int32_t sh_frame, const int32_t* row_of, const float* grad_vinv, const float* grad_alpha,
+                       const float* grad_l_d, const float* grad_depth, float cov_eps, int32_t clamp_colour, const float* grad_mean_xy,
+                       float* grad_mean, float* grad_quat, float* grad_log_scale, float* grad_opacity_logit, float* grad_sh_coeff,
+                       void* stream) {
+  if (clamp_colour != 0 && clamp_colour != 1) return GCP_ERR_INVALID_ARGUMENT;
+  return gcp_splat_backward_flags(mean, quat_xyzw, log_scale, opacity_logit, sh_coeff, cam_P, cam_K, n_gauss, sh_degree, n_basis, sh_frame,
+                                  row_of, grad_vinv, grad_alpha, grad_l_d, grad_depth, cov_eps, clamp_colour ? GCP_SPLAT_CLAMP_COLOUR : 0,
+                                  grad_mean_xy, grad_mean, grad_quat, grad_log_scale, grad_opacity_logit, grad_sh_coeff, stream);
 }
 
 }  // extern "C"

@@ -41,8 +41,8 @@ CENTRES = ("pixel", "subpixel")
 DENSIFY_ON = ("position", "screen")
 
 
-def _splat_options(centres, cov_dilation, clamp_colour):
-    """Validated (centres, cov_eps, clamp_colour) of `camera_inputs`; ValueError before anything touches the GPU."""
+def _splat_options(centres, cov_dilation, clamp_colour, antialias=False):
+    """Validated (centres, cov_eps, clamp_colour, antialias) of `camera_inputs`; ValueError before anything touches the GPU."""
     if centres not in CENTRES:
         raise ValueError(f"centres: 'pixel' or 'subpixel', got {centres!r}")
     cov_eps = 1e-6 if cov_dilation is None else cov_dilation
@@ -50,7 +50,11 @@ def _splat_options(centres, cov_dilation, clamp_colour):
         raise ValueError(f"cov_dilation: None or a finite number >= 0, got {cov_dilation!r}")
     if not isinstance(clamp_colour, bool):
         raise ValueError(f"clamp_colour: True or False, got {clamp_colour!r}")
-    return centres, float(cov_eps), clamp_colour
+    if not isinstance(antialias, bool):
+        raise ValueError(f"antialias: True or False, got {antialias!r}")
+    if antialias and not (cov_dilation is not None and cov_dilation > 0):
+        raise ValueError(f"antialias=True compensates the opacity for a covariance dilation: cov_dilation must be > 0, got {cov_dilation!r}")
+    return centres, float(cov_eps), clamp_colour, antialias
 
 __all__ = [
     "GS_dataset",
@@ -123,6 +127,8 @@ class _ProjectCamera(torch.autograd.Function):
     `subpixel` — the pixel centre kept as float32 (m, 2) at px + 0.5, differentiable: its gradient is handed to the backward
     as grad_mean_xy.  Not `subpixel`: the centre is truncated as by default and returned as int32 without a gradient (the box
     still goes around the untruncated centre, by the rule of the float one).
+    splat=(subpixel, cov_eps, clamp_colour, antialias): a fourth field, absent = False.  True: gcp_splat_forward_flags and
+    gcp_splat_backward_flags with GCP_SPLAT_ANTIALIAS set — alpha is sigmoid(opacity) rho, rho = sqrt(det Sigma / det Sigma').
     Returns (vinv, alpha, l_d, [depth,] mean_xy, start, end, boxsize, index, keep)."""
 
     @staticmethod
@@ -147,6 +153,9 @@ class _ProjectCamera(torch.autograd.Function):
             made = (record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream)
             if splat is None:
                 _lib.check(lib.gcp_project_forward_sh(*world, *made), "gcp_project_forward")
+            elif len(splat) > 3 and splat[3]:
+                flags = _lib.SPLAT_ANTIALIAS | (_lib.SPLAT_CLAMP_COLOUR if splat[2] else 0)
+                _lib.check(lib.gcp_splat_forward_flags(*world, splat[1], 0.5 if subpixel else 0.0, flags, *made), "gcp_splat_forward_flags")
             else:
                 _lib.check(lib.gcp_splat_forward(*world, splat[1], 0.5 if subpixel else 0.0, int(splat[2]), *made), "gcp_splat_forward")
             # the one device->host read: sizes of the outputs.  capture_safe: none — the list keeps all n Gaussians, the
@@ -193,6 +202,10 @@ class _ProjectCamera(torch.autograd.Function):
             lib = _lib.load()
             if splat is None:
                 _lib.check(lib.gcp_project_backward_sh(*upstream, *made), "gcp_project_backward")
+            elif len(splat) > 3 and splat[3]:
+                flags = _lib.SPLAT_ANTIALIAS | (_lib.SPLAT_CLAMP_COLOUR if splat[2] else 0)
+                _lib.check(lib.gcp_splat_backward_flags(*upstream, splat[1], flags, g[-1].data_ptr() if subpixel else None, *made),
+                           "gcp_splat_backward_flags")
             else:
                 _lib.check(lib.gcp_splat_backward(*upstream, splat[1], int(splat[2]), g[-1].data_ptr() if subpixel else None, *made),
                            "gcp_splat_backward")
@@ -200,7 +213,7 @@ class _ProjectCamera(torch.autograd.Function):
 
 
 def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
-                  with_depth=False, sh_frame="camera", centres="pixel", cov_dilation=None, clamp_colour=False):
+                  with_depth=False, sh_frame="camera", centres="pixel", cov_dilation=None, clamp_colour=False, antialias=False):
     """Per camera, the depth-ordered, culled arguments of the Function (reference: gs_model.py:277-425).
 
     mean (N,3), variance_q (N,4 xyzw), variance_scale (N,3 log), opacity (N,1 logit), color (N,(L+1)^2,3),
@@ -234,12 +247,20 @@ def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, ti
     is ceil(c - h) .. floor(c + h) around the float centre c, h = the clamped 3-sigma half extent.
     cov_dilation=F (finite, >= 0; None = 1e-6, the reference's): F is added to the diagonal of the pixel covariance (0.3: the
     usual screen-space dilation).  clamp_colour=True: l_d = max(SH sum, 0) per channel, no gradient through a clamped channel.
-    centres="pixel" with a dilation or the clamp: "mean" stays int32, truncated as by default, without a gradient."""
+    centres="pixel" with a dilation or the clamp: "mean" stays int32, truncated as by default, without a gradient.
+    antialias=True (needs cov_dilation > 0; ValueError otherwise): the opacity compensation of the dilation.  The dilated
+    covariance Sigma' = Sigma + F I paints sqrt(det Sigma' / det Sigma) times the energy of the Gaussian it replaces — up to
+    8.5 x for one of 0.2 px; "opacity" becomes sigmoid(opacity) rho with rho = sqrt(det Sigma / det Sigma') (det Sigma' with
+    the 1e-6 "variance_inverse" is formed with), and rho's exact gradient reaches mean, variance_q and variance_scale.  A
+    Gaussian whose det Sigma is <= 0 in float32 has rho = 0 and gets no gradient through it.  Every other entry is bit for
+    bit what it is without the option.  Mip-Splatting's 2-D filter; the "antialiased" mode of other renderers."""
     if sh_frame not in SH_FRAMES:
         raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
-    centres, cov_eps, clamp_colour = _splat_options(centres, cov_dilation, clamp_colour)
+    centres, cov_eps, clamp_colour, antialias = _splat_options(centres, cov_dilation, clamp_colour, antialias)
     # None: the defaults, on the kernels of csrc/gcp_project.hip
     splat = (centres == "subpixel", cov_eps, clamp_colour) if centres != "pixel" or cov_dilation is not None or clamp_colour else None
+    if antialias:  # validated: there is a dilation, so `splat` is set
+        splat = (*splat, True)
     width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
     clamp = _box_clamp(width, height, tile_max_width)
     grad_iter = None
@@ -359,10 +380,13 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
-                 active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position"):
+                 active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position",
+                 antialias=False):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
         the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
-        clamp_colour: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
+        clamp_colour, antialias: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
+        antialias scales the opacity the blend sees, not the parameter: pruning (`densify_and_prune`,
+        `densify_and_prune_device`) and `reset_opacity` keep testing the raw sigmoid(opacity), and `save_ply` stores it.
         densify_on: the statistic `densify_and_prune_device` decides on.  "position" (the default, the reference's): the norm
         of the 3-D positional gradient per step, kept by `param_iter_update`.  "screen" (needs centres="subpixel"): the norm
         of the loss's gradient with respect to the 2-D splat centre, per VIEW, scaled by (W/2, H/2) — the NDC unit other
@@ -395,9 +419,9 @@ class GS_model_with_param(torch.nn.Module):
                                                  lr_delay_mult=position_lr_delay_mult, max_steps=position_lr_max_steps)
         self.lr = {"mean": self.mean_lr_setfunc(0), "variance_q": rotation_lr, "variance_scale": scaling_lr,
                    "opacity": opacity_lr, "color": feature_lr}
-        _splat_options(centres, cov_dilation, clamp_colour)
+        _splat_options(centres, cov_dilation, clamp_colour, antialias)
         self._L_max, self.sh_frame, self.active_sh_degree = L_max, sh_frame, active_sh_degree
-        self.centres, self.cov_dilation, self.clamp_colour = centres, cov_dilation, clamp_colour
+        self.centres, self.cov_dilation, self.clamp_colour, self.antialias = centres, cov_dilation, clamp_colour, antialias
         self.reference_layout = reference_layout
         self.mean_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
         self.mean_grads_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int16)
@@ -544,7 +568,7 @@ class GS_model_with_param(torch.nn.Module):
         g >= grad_threshold, every Gaussian takes one action, decided on the state before the call: split (hot,
         s > percent_dense * extent: `n_split` children sampled from it, of scale s / (0.8 n_split), replace it), clone (hot
         otherwise: the Gaussian and one copy) or keep; then the rows it would write are dropped if
-        sigmoid(opacity) < prunning_min_opacity or their largest scale > 0.1 * extent.  This is the clone -> split -> prune
+        sigmoid(opacity) < prunning_min_opacity (the raw opacity, also under antialias=True) or their largest scale > 0.1 * extent.  This is the clone -> split -> prune
         sequence of other 3DGS trainers with zero statistics on new rows; `densify_and_prune` (the reference's order) lets
         split children inherit the parent's statistic, so they may be cloned in the same call.
         Rows come out in Gaussian order, a Gaussian's rows next to each other.  A surviving row keeps its exp_avg /
@@ -649,7 +673,7 @@ class GS_model_with_param(torch.nn.Module):
         return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
                              self.variance_pixel_tile_max_width, self.active_sh_degree, capture_safe=capture_safe,
                              with_depth=with_depth, sh_frame=self.sh_frame, centres=self.centres, cov_dilation=self.cov_dilation,
-                             clamp_colour=self.clamp_colour)
+                             clamp_colour=self.clamp_colour, antialias=self.antialias)
 
     # ---- scene files (ply_io) ------------------------------------------------------------------------------------
     def save_ply(self, path, convention="3dgs"):

@@ -6,8 +6,9 @@ of a step grows with the pair count, not with the kernels.
     python tools/splat_bench.py ROOT MODE [REPEATS]
 
 ROOT: the checkout whose package is measured ("." or another commit's tree with its library built: run one process per
-tree, alternating, to set this commit against its parent); MODE: default | subpixel (centres="subpixel", cov_dilation=0.3).
-Prints one JSON line.  Results: profiles/r10_subpixel.md."""
+tree, alternating, to set this commit against its parent); MODE: default | subpixel (centres="subpixel", cov_dilation=0.3) |
+antialias (subpixel plus antialias=True).
+Prints one JSON line.  Results: profiles/r10_subpixel.md, profiles/r14_antialias.md."""
 import json
 import statistics
 import sys
@@ -24,7 +25,11 @@ dev = torch.device("cuda", 0)
 n, width, height = 1_000_000, 1920, 1080
 P, K, wh = ring_cameras(1, width, height, device=dev)
 mean, q, scale, op = make_world(n, width, sigma_px=2.0, seed=0, device=dev)
+if mode not in ("default", "subpixel", "antialias"):
+    sys.exit(f"MODE: default, subpixel or antialias, got {mode!r}")
 opts = {} if mode == "default" else {"centres": "subpixel", "cov_dilation": 0.3}
+if mode == "antialias":
+    opts["antialias"] = True
 model = gm.GS_model_with_param(mean, q, scale, op, **opts)
 with torch.no_grad():
     model.color[:, 1:] = 0.1 * torch.randn_like(model.color[:, 1:])
