@@ -1,6 +1,6 @@
 """PyTorch restatement, op for op, of the reference's model forward up to the Function call
 (reference: gs_model.py:277-425; helpers uitility.py:231-287, :431-462) — the checker of the fused projection kernels
-(csrc/gcp_project.hip).  Pinned against the reference's own forward run on CPU: tests/golden/forward_golden.npz
+(csrc/gcp_project.hip; their caller: simplegaussiansplat_tk71_amd/projection.py, `camera_inputs`).  Pinned against the reference's own forward run on CPU: tests/golden/forward_golden.npz
 (tests/test_gs_model.py::test_camera_inputs_match_reference_forward): integers bit-exact, floats to 1e-6.
 
 Differences from the reference's text, none of which changes a result on the golden scenes: the 3-sigma box comes

@@ -1,0 +1,78 @@
+"""Density control on the device (csrc/gcp_densify.hip): the screen-space statistic and the kernel sequence of the
+one-pass split / clone / prune.  What belongs to the model — parameters, optimiser, statistics — stays in
+`GS_model_with_param.densify_and_prune_device`."""
+import torch
+
+from . import _lib
+
+DENSIFY_ON = ("position", "screen")
+
+
+def accumulate_screen_grads(grad_xy, index, scale, norm_acc, view_count, validate=False):
+    """The screen-space densification statistic of one camera (gcp_densify_accumulate, csrc/gcp_densify.hip), in place:
+    norm_acc[index[i]] += |grad_xy[i] * scale|, view_count[index[i]] += 1.  grad_xy float32 (m, 2): the loss's gradient with
+    respect to the splat centres in list order; index int64 (m,): the list's Gaussian ids, each at most once (what
+    `camera_inputs` returns as "index"); scale = (sx, sy); norm_acc float32 (N,), view_count int32 (N,).  GPU tensors only.
+    An id outside [0, N) is never written through; validate=True reads the number of such ids back first (one host read)
+    and raises, with nothing accumulated."""
+    if not (grad_xy.is_cuda and index.is_cuda and norm_acc.is_cuda and view_count.is_cuda):
+        raise RuntimeError("the densification statistic is a HIP kernel: tensors must live on the GPU (no CPU path)")
+    m, n = index.numel(), norm_acc.numel()
+    if index.dtype != torch.int64 or norm_acc.dtype != torch.float32 or view_count.dtype != torch.int32:
+        raise RuntimeError("accumulate_screen_grads expects int64 ids, a float32 norm and an int32 view count")
+    if tuple(grad_xy.shape) != (m, 2) or view_count.numel() != n or not (norm_acc.is_contiguous() and view_count.is_contiguous()):
+        raise RuntimeError("accumulate_screen_grads expects grad_xy (m, 2), index (m,) and contiguous norm_acc, view_count of one length")
+    grad_xy, index = grad_xy.detach().float().contiguous(), index.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(norm_acc.device):
+        stream = torch.cuda.current_stream(norm_acc.device).cuda_stream
+        if validate:
+            bad = torch.zeros(1, dtype=torch.int32, device=norm_acc.device)
+            _lib.check(lib.gcp_densify_accumulate(None, index.data_ptr(), m, 1.0, 1.0, None, None, n, bad.data_ptr(), stream),
+                       "gcp_densify_accumulate")
+            if int(bad):
+                raise RuntimeError(f"accumulate_screen_grads: {int(bad)} of {m} ids lie outside [0, {n})")
+        _lib.check(lib.gcp_densify_accumulate(grad_xy.data_ptr(), index.data_ptr(), m, float(scale[0]), float(scale[1]), norm_acc.data_ptr(),
+                                              view_count.data_ptr(), n, None, stream), "gcp_densify_accumulate")
+
+
+def densify_rows(params, moments, norm, views, grad_threshold, split_scale, prune_scale, min_opacity, n_split, seed):
+    """The kernel sequence of `GS_model_with_param.densify_and_prune_device`, whose docstring states the rule: plan (an action
+    and a row count per Gaussian, their offsets), the one 4-byte device->host read of the new row count m, fill (source row
+    and kind of every new row), the row gathers, split (the children's samples over the gathered mean and scale).
+    params: {"mean", "variance_q", "variance_scale", "opacity", "color"} -> contiguous float32 (n, ...); moments: name ->
+    (exp_avg, exp_avg_sq) of the parameters that have an optimiser state; norm float32 (n,), views int32 (n,): the statistic,
+    contiguous; a Gaussian is hot at norm / max(views, 1) >= grad_threshold, splits above split_scale, and a row is dropped
+    above prune_scale or below min_opacity; seed: 64 bits.
+    -> (new params by name, new (exp_avg, exp_avg_sq) by name — fresh rows 0.0 —, m)"""
+    dev, n = params["mean"].device, params["mean"].shape[0]
+    lib = _lib.load()
+    count, offset = (torch.empty(k, dtype=torch.int32, device=dev) for k in (n, n + 1))
+    action = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.gcp_densify_plan_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    seed = int(seed) & (2 ** 64 - 1)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gcp_densify_plan(norm.data_ptr(), views.data_ptr(), params["variance_scale"].data_ptr(), params["opacity"].data_ptr(), n,
+                                        float(grad_threshold), float(split_scale), float(prune_scale), float(min_opacity), int(n_split),
+                                        count.data_ptr(), action.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   "gcp_densify_plan")
+        m = int(offset[n])  # the one device->host read
+        src_row = torch.empty(m, dtype=torch.int32, device=dev)
+        kind = torch.empty(m, dtype=torch.uint8, device=dev)
+        _lib.check(lib.gcp_densify_fill(action.data_ptr(), offset.data_ptr(), n, m, src_row.data_ptr(), kind.data_ptr(), stream),
+                   "gcp_densify_fill")
+
+        def rows(t, mode):
+            out = torch.empty((m, *t.shape[1:]), dtype=torch.float32, device=dev)
+            _lib.check(lib.gcp_densify_rows(t.data_ptr(), n, src_row.data_ptr(), kind.data_ptr(), m, t[0].numel() if n else 0, mode,
+                                            out.data_ptr(), stream), "gcp_densify_rows")
+            return out
+
+        new = {k: rows(t, 0) for k, t in params.items()}
+        _lib.check(lib.gcp_densify_split(params["mean"].data_ptr(), params["variance_q"].data_ptr(), params["variance_scale"].data_ptr(),
+                                         src_row.data_ptr(), kind.data_ptr(), offset.data_ptr(), n, m, int(n_split), seed & 0xFFFFFFFF,
+                                         seed >> 32, new["mean"].data_ptr(), new["variance_scale"].data_ptr(), stream),
+                   "gcp_densify_split")
+        new_moments = {k: tuple(rows(t.contiguous(), 1) for t in pair) for k, pair in moments.items()}
+    return new, new_moments, m

@@ -5,56 +5,29 @@ Mirrors the reference's model class (reference: gs_model.py:123-460, `GS_model_w
 `[images, image_sample, grad_iter]`, same per-parameter Adam learning rates, densify / prune / opacity reset.
 Row f4 of SURVEY.md §8: this is caller integration, PyTorch on the GPU around the HIP Function — not a kernel.
 
-The projection (`camera_inputs`, reference: gs_model.py:277-425) is pinned, through its PyTorch restatement in
-oracle/gs_forward_torch.py, against the reference's own forward run on CPU (tests/golden/forward_golden.npz: the
-arguments the reference hands to `custom_autograd_grouped_cumprod.apply`).  Differences, all deliberate:
-  * the 3-sigma box comes from a closed-form 2x2 eigen-decomposition on the device; the reference moves every
-    covariance to the CPU for `torch.linalg.eigh` and back (gs_model.py:327-332).  For a positive semi-definite
-    matrix `V^2 |lambda|` is just its diagonal, so the box is 3*sqrt(diag) exactly;
-  * the depth sort is stable (the reference's `torch.argsort`, :356, leaves ties undefined);
+This module holds the model and dataset classes and the reference's small helpers.  What the model calls lives next to
+it and is re-exported from here under the names it always had: the camera projection (projection.py: `camera_inputs`),
+the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
+(density.py: `accumulate_screen_grads`).  Differences from the reference's class, all deliberate (those of the projection:
+projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
   * one Function call per camera, never chunked (nothing of pair-list size exists here; gs_model.py:428);
-  * the SH colour stands in for the reference's `sh_utility.eval_sh`, which is not in its checkout
-    (gs_model.py:9,335): real spherical harmonics up to degree 3 in the usual 3DGS order and sign — parity unpinned.
-    The direction they are evaluated on is, by default, the reference's: -t/|t| in CAMERA coordinates (:335-338), so a
-    Gaussian changes colour when the camera rolls; `sh_frame="world"` uses the world-space unit vector from the camera
-    centre to the Gaussian, the convention of other 3DGS renderers (what a scene saved with `save_ply` needs);
   * tensors live on the parameters' device instead of a hard-coded "cuda";
-  * on the GPU the whole per-Gaussian chain is ONE HIP kernel per camera and direction (`gcp_project_forward`,
-    `gcp_project_backward`, csrc/gcp_project.hip) instead of ~150 PyTorch kernels: at 10^6 Gaussians the reference's
-    formulation costs 64 ms forward + 110 ms backward around a 1.8 ms Function.  That formulation is kept, as the
-    checker the kernels are tested against, in oracle/gs_forward_torch.py — not here: projection and loss have no
-    CPU path (CPU tensors raise).
+  * projection and loss have no CPU path (CPU tensors raise).
 """
 import math
-import numbers
 
 import torch
 
-from . import _lib
-from . import raster as _raster
+from . import density
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
+from .density import DENSIFY_ON, accumulate_screen_grads
+from .loss import splat_loss
+from .optim import HipAdam
+from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
-SH_FRAMES = {"camera": 0, "world": 1}
-CENTRES = ("pixel", "subpixel")
-DENSIFY_ON = ("position", "screen")
-
-
-def _splat_options(centres, cov_dilation, clamp_colour, antialias=False):
-    """Validated (centres, cov_eps, clamp_colour, antialias) of `camera_inputs`; ValueError before anything touches the GPU."""
-    if centres not in CENTRES:
-        raise ValueError(f"centres: 'pixel' or 'subpixel', got {centres!r}")
-    cov_eps = 1e-6 if cov_dilation is None else cov_dilation
-    if isinstance(cov_eps, bool) or not isinstance(cov_eps, numbers.Real) or not (math.isfinite(cov_eps) and cov_eps >= 0):
-        raise ValueError(f"cov_dilation: None or a finite number >= 0, got {cov_dilation!r}")
-    if not isinstance(clamp_colour, bool):
-        raise ValueError(f"clamp_colour: True or False, got {clamp_colour!r}")
-    if not isinstance(antialias, bool):
-        raise ValueError(f"antialias: True or False, got {antialias!r}")
-    if antialias and not (cov_dilation is not None and cov_dilation > 0):
-        raise ValueError(f"antialias=True compensates the opacity for a covariance dilation: cov_dilation must be > 0, got {cov_dilation!r}")
-    return centres, float(cov_eps), clamp_colour, antialias
+PARAM_NAMES = ("mean", "variance_q", "variance_scale", "opacity", "color")  # the per-Gaussian parameters, in optimiser order
 
 __all__ = [
     "GS_dataset",
@@ -67,6 +40,7 @@ __all__ = [
     "mean_neighbour_distance",
     "splat_loss",
 ]
+
 
 def qvec_to_rotmat_batch(q):
     """(N, 4) unit quaternions in (x, y, z, w) order -> (N, 3, 3) (reference: uitility.py:231-254)."""
@@ -100,252 +74,6 @@ def mean_neighbour_distance(n, cloud, batch_size=2000):
         d = torch.cdist(cloud[i:i + batch_size], cloud)
         out[i:i + batch_size] = torch.topk(d, min(n, d.shape[1]), dim=1, largest=False).values.mean(dim=1, keepdim=True)
     return out.repeat(1, 3)
-
-
-_CLAMP_CACHE = {}
-
-
-def _box_clamp(width, height, tile_max_width):
-    """Upper bound of the 3-sigma half extents: 10 * sqrt(W*H) * sigmoid(tile_max_width) in float32, as the reference forms
-    it (gs_model.py:364-365).  Evaluated once per (W, H, setting) on the host: no device work, no read-back."""
-    key = (width, height, float(tile_max_width))
-    if key not in _CLAMP_CACHE:
-        t = torch.sqrt(torch.tensor(width * height, dtype=torch.int32).to(torch.float32)) * torch.sigmoid(
-            torch.tensor(float(tile_max_width), dtype=torch.float32))
-        _CLAMP_CACHE[key] = (t * 10).item()
-    return _CLAMP_CACHE[key]
-
-
-class _ProjectCamera(torch.autograd.Function):
-    """One camera of `camera_inputs` on the HIP library: the projection's forward kernel, the library's stable radix sort on
-    the depth keys, its gather; backward = its backward kernel.  `L_max` is the ACTIVE degree, which may be below what `color`
-    stores; `sh_frame` 0 / 1 = camera / world directions; with_depth: the camera-space depths too, right after l_d.
-    splat=None: the reference's conventions, on the kernels of csrc/gcp_project.hip (gcp_project_forward_sh,
-    gcp_project_gather or gcp_project_gather_depth, gcp_project_backward_sh); the centre is int32 (m, 2) without a gradient.
-    splat=(subpixel, cov_eps, clamp_colour): the kernels of csrc/gcp_splat.hip (gcp_splat_forward, gcp_splat_gather,
-    gcp_splat_backward): `cov_eps` on the diagonal of the pixel covariance, the SH colour clamped at 0 (`clamp_colour`), and —
-    `subpixel` — the pixel centre kept as float32 (m, 2) at px + 0.5, differentiable: its gradient is handed to the backward
-    as grad_mean_xy.  Not `subpixel`: the centre is truncated as by default and returned as int32 without a gradient (the box
-    still goes around the untruncated centre, by the rule of the float one).
-    splat=(subpixel, cov_eps, clamp_colour, antialias): a fourth field, absent = False.  True: gcp_splat_forward_flags and
-    gcp_splat_backward_flags with GCP_SPLAT_ANTIALIAS set — alpha is sigmoid(opacity) rho, rho = sqrt(det Sigma / det Sigma').
-    Returns (vinv, alpha, l_d, [depth,] mean_xy, start, end, boxsize, index, keep)."""
-
-    @staticmethod
-    def forward(ctx, mean, variance_q, variance_scale, opacity, color, cam_P, cam_K, width, height, box_clamp, L_max,
-                capture_safe=False, with_depth=False, sh_frame=0, splat=None):
-        dev, n = mean.device, mean.shape[0]
-        args = [t.detach().contiguous() for t in (mean, variance_q, variance_scale, opacity, color, cam_P, cam_K)]
-        for t in args:
-            if t.dtype != torch.float32 or t.device != dev:
-                raise RuntimeError("projection expects float32 tensors on one device")
-        if not mean.is_cuda:
-            raise RuntimeError("the fused projection is a HIP kernel: tensors must live on the GPU (no CPU path)")
-        lib = _lib.load()
-        subpixel = splat is not None and splat[0]
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)  # noqa: E731
-        record, sort_key, row_of = f32(n, 16), i32(n), i32(n)
-        keep = torch.empty(n, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            world = (*(t.data_ptr() for t in args), n, L_max, color.shape[1], sh_frame, width, height, box_clamp)
-            made = (record.data_ptr(), sort_key.data_ptr(), keep.data_ptr(), row_of.data_ptr(), stream)
-            if splat is None:
-                _lib.check(lib.gcp_project_forward_sh(*world, *made), "gcp_project_forward")
-            elif len(splat) > 3 and splat[3]:
-                flags = _lib.SPLAT_ANTIALIAS | (_lib.SPLAT_CLAMP_COLOUR if splat[2] else 0)
-                _lib.check(lib.gcp_splat_forward_flags(*world, splat[1], 0.5 if subpixel else 0.0, flags, *made), "gcp_splat_forward_flags")
-            else:
-                _lib.check(lib.gcp_splat_forward(*world, splat[1], 0.5 if subpixel else 0.0, int(splat[2]), *made), "gcp_splat_forward")
-            # the one device->host read: sizes of the outputs.  capture_safe: none — the list keeps all n Gaussians, the
-            # culled ones behind the kept ones with empty boxes (the gather with the keep mask)
-            m = n if capture_safe else (int(keep.sum()) if n else 0)
-            # culled Gaussians carry the largest key: the first m entries of the stable permutation are the kept ones in
-            # depth order, ties in the Gaussians' own order
-            perm = _raster.stable_sort_keys(sort_key, key_bits=31)[1] if n else sort_key
-            start, end, boxsize = i32(m, 2), i32(m, 2), torch.empty(m, dtype=torch.int64, device=dev)
-            mean_xy = i32(m, 2) if splat is None else f32(m, 2)
-            vinv, alpha, l_d, index = f32(m, 2, 2), f32(m, 1), f32(m, 3), torch.empty(m, dtype=torch.int64, device=dev)
-            depth = f32(m) if with_depth else None
-            lists = (record.data_ptr(), perm.data_ptr(), m, start.data_ptr(), end.data_ptr(), mean_xy.data_ptr(), boxsize.data_ptr(),
-                     vinv.data_ptr(), alpha.data_ptr(), l_d.data_ptr())
-            rows = (index.data_ptr(), row_of.data_ptr(), keep.data_ptr() if capture_safe else None, stream)
-            if splat is not None:
-                _lib.check(lib.gcp_splat_gather(*lists, depth.data_ptr() if with_depth else None, *rows), "gcp_splat_gather")
-            elif with_depth:
-                _lib.check(lib.gcp_project_gather_depth(*lists, depth.data_ptr(), *rows), "gcp_project_gather_depth")
-            else:
-                _lib.check(lib.gcp_project_gather(*lists, *rows), "gcp_project_gather")
-        if splat is not None and not subpixel:
-            mean_xy = mean_xy.to(torch.int32)  # towards zero, as the kernels of gcp_project.hip convert
-        keep = keep.view(torch.bool)
-        ctx.save_for_backward(*args, row_of)
-        ctx.L_max, ctx.with_depth, ctx.sh_frame, ctx.splat = L_max, with_depth, sh_frame, splat
-        out = (vinv, alpha, l_d, *((depth,) if with_depth else ()), mean_xy, start, end, boxsize, index, keep)
-        ctx.mark_non_differentiable(*out[-(5 if subpixel else 6):])
-        return out
-
-    @staticmethod
-    def backward(ctx, g_vinv, g_alpha, g_ld, *rest):
-        *args, row_of = ctx.saved_tensors
-        mean, variance_q, variance_scale, opacity, color = args[:5]
-        splat = ctx.splat
-        subpixel = splat is not None and splat[0]
-        grads = [torch.empty_like(t) for t in (mean, variance_q, variance_scale, opacity, color)]  # every row is written
-        g = [t.contiguous().float() for t in (g_vinv, g_alpha, g_ld, *rest[:int(ctx.with_depth) + int(subpixel)])]
-        g_depth = g[3].data_ptr() if ctx.with_depth else None
-        with torch.cuda.device(mean.device):
-            upstream = (*(t.data_ptr() for t in args), mean.shape[0], ctx.L_max, color.shape[1], ctx.sh_frame, row_of.data_ptr(),
-                        *(t.data_ptr() for t in g[:3]), g_depth)
-            made = (*(t.data_ptr() for t in grads), torch.cuda.current_stream(mean.device).cuda_stream)
-            lib = _lib.load()
-            if splat is None:
-                _lib.check(lib.gcp_project_backward_sh(*upstream, *made), "gcp_project_backward")
-            elif len(splat) > 3 and splat[3]:
-                flags = _lib.SPLAT_ANTIALIAS | (_lib.SPLAT_CLAMP_COLOUR if splat[2] else 0)
-                _lib.check(lib.gcp_splat_backward_flags(*upstream, splat[1], flags, g[-1].data_ptr() if subpixel else None, *made),
-                           "gcp_splat_backward_flags")
-            else:
-                _lib.check(lib.gcp_splat_backward(*upstream, splat[1], int(splat[2]), g[-1].data_ptr() if subpixel else None, *made),
-                           "gcp_splat_backward")
-        return (*grads, *[None] * 10)
-
-
-def camera_inputs(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max=2, capture_safe=False,
-                  with_depth=False, sh_frame="camera", centres="pixel", cov_dilation=None, clamp_colour=False, antialias=False):
-    """Per camera, the depth-ordered, culled arguments of the Function (reference: gs_model.py:277-425).
-
-    mean (N,3), variance_q (N,4 xyzw), variance_scale (N,3 log), opacity (N,1 logit), color (N,(L+1)^2,3),
-    P (C,3,4) world->camera, K (C,3,3), wh (C,2), tile_max_width = logit of the box clamp as a fraction of
-    sqrt(W*H)/10.  Returns a list with one dict per camera (None where nothing is visible, :414-417) holding
-    boxsize, startpoint, endpoint, mean, variance_inverse, opacity, l_d, index (Gaussian ids, depth order),
-    and the (N,) bool `grad_iter` of Gaussians seen by any camera (:401-407).
-
-    One HIP kernel per camera and direction (csrc/gcp_project.hip); GPU tensors only — there is no CPU path.  The
-    reference's op-by-op PyTorch formulation lives in oracle/gs_forward_torch.py as the checker.
-
-    capture_safe=True: no device->host read at all (pass `wh` as a CPU tensor or a list): every camera's list keeps all N
-    Gaussians in depth order, the culled ones behind the kept ones with EMPTY boxes (binned into no tile, zero
-    gradients), and no camera is ever dropped; images and gradients are those of the default mode.  Together with
-    `cuda_kernel.tile_capacity` the projection + Function forward and backward queue without waiting for the GPU.
-
-    with_depth=True: every dict also holds "depth", the Gaussians' camera-space depths in list order (the positive depth
-    they are sorted by; 0 for the culled entries of a capture-safe list), differentiable w.r.t. `mean` — the `depth`
-    argument of `cuda_kernel.render`.
-
-    L_max (0..3) is the ACTIVE SH degree: `color` may store more rows than (L_max+1)^2; those are not read and get exact
-    zero gradients.  sh_frame: "camera" (the default, the reference's: the SH basis is evaluated on -t/|t| in camera
-    coordinates) or "world" (on the world-space unit vector from the camera centre to the Gaussian, as other 3DGS
-    renderers do: the colour does not change when the camera rolls).
-
-    Three more conventions of other 3DGS renderers, opt-in (csrc/gcp_splat.hip; with the defaults nothing below runs):
-    centres="subpixel": "mean" is float32 (m, 2) and differentiable — the projected centre px + 0.5 instead of trunc(px), so
-    that the blend's gradient w.r.t. the centre reaches `mean` (with "pixel" a Gaussian's position is trained only through
-    the Jacobian, the view direction and the depth).  The 0.5: pixel i of the cropped image is frame pixel i + 1 and its
-    centre lies at i + 0.5 in the coordinates of K (COLMAP / 3DGS), so dx = (i + 1) - (px + 0.5) = (i + 0.5) - px.  The box
-    is ceil(c - h) .. floor(c + h) around the float centre c, h = the clamped 3-sigma half extent.
-    cov_dilation=F (finite, >= 0; None = 1e-6, the reference's): F is added to the diagonal of the pixel covariance (0.3: the
-    usual screen-space dilation).  clamp_colour=True: l_d = max(SH sum, 0) per channel, no gradient through a clamped channel.
-    centres="pixel" with a dilation or the clamp: "mean" stays int32, truncated as by default, without a gradient.
-    antialias=True (needs cov_dilation > 0; ValueError otherwise): the opacity compensation of the dilation.  The dilated
-    covariance Sigma' = Sigma + F I paints sqrt(det Sigma' / det Sigma) times the energy of the Gaussian it replaces — up to
-    8.5 x for one of 0.2 px; "opacity" becomes sigmoid(opacity) rho with rho = sqrt(det Sigma / det Sigma') (det Sigma' with
-    the 1e-6 "variance_inverse" is formed with), and rho's exact gradient reaches mean, variance_q and variance_scale.  A
-    Gaussian whose det Sigma is <= 0 in float32 has rho = 0 and gets no gradient through it.  Every other entry is bit for
-    bit what it is without the option.  Mip-Splatting's 2-D filter; the "antialiased" mode of other renderers."""
-    if sh_frame not in SH_FRAMES:
-        raise ValueError(f"sh_frame: 'camera' or 'world', got {sh_frame!r}")
-    centres, cov_eps, clamp_colour, antialias = _splat_options(centres, cov_dilation, clamp_colour, antialias)
-    # None: the defaults, on the kernels of csrc/gcp_project.hip
-    splat = (centres == "subpixel", cov_eps, clamp_colour) if centres != "pixel" or cov_dilation is not None or clamp_colour else None
-    if antialias:  # validated: there is a dilation, so `splat` is set
-        splat = (*splat, True)
-    width, height = (int(v) for v in (wh[0].tolist() if isinstance(wh, torch.Tensor) else wh[0]))  # device `wh`: one read (.to(int32) truncates, :279)
-    clamp = _box_clamp(width, height, tile_max_width)
-    grad_iter = None
-    cams = []
-    for c in range(P.shape[0]):
-        out = _ProjectCamera.apply(mean, variance_q, variance_scale, opacity, color, P[c], K[c], width, height, clamp, L_max,
-                                   capture_safe, with_depth, SH_FRAMES[sh_frame], splat)
-        mean_xy, start, end, boxsize, index, keep = out[-6:]
-        vinv, alpha, l_d = out[:3]
-        grad_iter = keep if grad_iter is None else grad_iter | keep
-        cam = None if index.numel() == 0 else {
-            "boxsize": boxsize, "startpoint": start, "endpoint": end, "mean": mean_xy, "variance_inverse": vinv,
-            "opacity": alpha, "l_d": l_d, "index": index}
-        if cam is not None and with_depth:
-            cam["depth"] = out[3]
-        cams.append(cam)
-    if grad_iter is None:
-        grad_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.bool)
-    return cams, grad_iter, (width, height)
-
-
-def accumulate_screen_grads(grad_xy, index, scale, norm_acc, view_count, validate=False):
-    """The screen-space densification statistic of one camera (gcp_densify_accumulate, csrc/gcp_densify.hip), in place:
-    norm_acc[index[i]] += |grad_xy[i] * scale|, view_count[index[i]] += 1.  grad_xy float32 (m, 2): the loss's gradient with
-    respect to the splat centres in list order; index int64 (m,): the list's Gaussian ids, each at most once (what
-    `camera_inputs` returns as "index"); scale = (sx, sy); norm_acc float32 (N,), view_count int32 (N,).  GPU tensors only.
-    An id outside [0, N) is never written through; validate=True reads the number of such ids back first (one host read)
-    and raises, with nothing accumulated."""
-    if not (grad_xy.is_cuda and index.is_cuda and norm_acc.is_cuda and view_count.is_cuda):
-        raise RuntimeError("the densification statistic is a HIP kernel: tensors must live on the GPU (no CPU path)")
-    m, n = index.numel(), norm_acc.numel()
-    if index.dtype != torch.int64 or norm_acc.dtype != torch.float32 or view_count.dtype != torch.int32:
-        raise RuntimeError("accumulate_screen_grads expects int64 ids, a float32 norm and an int32 view count")
-    if tuple(grad_xy.shape) != (m, 2) or view_count.numel() != n or not (norm_acc.is_contiguous() and view_count.is_contiguous()):
-        raise RuntimeError("accumulate_screen_grads expects grad_xy (m, 2), index (m,) and contiguous norm_acc, view_count of one length")
-    grad_xy, index = grad_xy.detach().float().contiguous(), index.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(norm_acc.device):
-        stream = torch.cuda.current_stream(norm_acc.device).cuda_stream
-        if validate:
-            bad = torch.zeros(1, dtype=torch.int32, device=norm_acc.device)
-            _lib.check(lib.gcp_densify_accumulate(None, index.data_ptr(), m, 1.0, 1.0, None, None, n, bad.data_ptr(), stream),
-                       "gcp_densify_accumulate")
-            if int(bad):
-                raise RuntimeError(f"accumulate_screen_grads: {int(bad)} of {m} ids lie outside [0, {n})")
-        _lib.check(lib.gcp_densify_accumulate(grad_xy.data_ptr(), index.data_ptr(), m, float(scale[0]), float(scale[1]), norm_acc.data_ptr(),
-                                              view_count.data_ptr(), n, None, stream), "gcp_densify_accumulate")
-
-
-class HipAdam:
-    """torch.optim.Adam's update (default betas / eps, no weight decay, no amsgrad — what the reference constructs at
-    gs_model.py:43-47) on the HIP library: one streaming kernel per parameter tensor (csrc/gcp_optim.hip, gcp_adam_step)
-    instead of torch's multi-tensor launches (0.38 -> 0.2 ms per step at 10^6 Gaussians).  Same interface as far as the
-    model uses it: `param_groups` with one tensor and an `lr` each, `step()`, `zero_grad()`."""
-
-    def __init__(self, param_groups, betas=(0.9, 0.999), eps=1e-8):
-        self.param_groups = [dict(g, params=list(g["params"]) if isinstance(g["params"], (list, tuple)) else [g["params"]])
-                             for g in param_groups]
-        self.betas, self.eps = betas, eps
-        self.state = {}
-
-    @torch.no_grad()
-    def step(self):
-        lib = _lib.load()
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("HipAdam updates contiguous float32 GPU tensors")
-                st = self.state.setdefault(p, {"step": 0, "exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)})
-                st["step"] += 1
-                grad = p.grad.contiguous()
-                with torch.cuda.device(p.device):
-                    _lib.check(lib.gcp_adam_step(p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                                 p.numel(), float(group["lr"]), self.betas[0], self.betas[1], self.eps, st["step"],
-                                                 torch.cuda.current_stream(p.device).cuda_stream), "gcp_adam_step")
-
-    def zero_grad(self, set_to_none=True):
-        for group in self.param_groups:
-            for p in group["params"]:
-                if set_to_none:
-                    p.grad = None
-                elif p.grad is not None:
-                    p.grad.zero_()
 
 
 class GS_dataset(torch.utils.data.Dataset):
@@ -419,15 +147,12 @@ class GS_model_with_param(torch.nn.Module):
                                                  lr_delay_mult=position_lr_delay_mult, max_steps=position_lr_max_steps)
         self.lr = {"mean": self.mean_lr_setfunc(0), "variance_q": rotation_lr, "variance_scale": scaling_lr,
                    "opacity": opacity_lr, "color": feature_lr}
-        _splat_options(centres, cov_dilation, clamp_colour, antialias)
+        splat_options(centres, cov_dilation, clamp_colour, antialias)  # validation only: `camera_inputs` forms the record
         self._L_max, self.sh_frame, self.active_sh_degree = L_max, sh_frame, active_sh_degree
         self.centres, self.cov_dilation, self.clamp_colour, self.antialias = centres, cov_dilation, clamp_colour, antialias
         self.reference_layout = reference_layout
-        self.mean_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
-        self.mean_grads_iter = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int16)
         self.densify_on = densify_on
-        self.screen_grads_norm = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.float32)
-        self.screen_grads_views = torch.zeros(mean.shape[0], device=mean.device, dtype=torch.int32)
+        self._zero_density_stats(mean.shape[0])
         self.changing_optimizer()
 
     # ---- optimiser plumbing (reference: gs_model.py:43-67) -------------------------------------------------
@@ -482,6 +207,14 @@ class GS_model_with_param(torch.nn.Module):
         return grad_iter
 
     # ---- densification statistics (:190-199) ----------------------------------------------------------------
+    def _zero_density_stats(self, n):
+        """Both statistics (see `densify_on`) at zero for `n` Gaussians."""
+        dev = self.mean.device
+        self.mean_grads_norm = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.mean_grads_iter = torch.zeros(n, device=dev, dtype=torch.int16)
+        self.screen_grads_norm = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.screen_grads_views = torch.zeros(n, device=dev, dtype=torch.int32)
+
     def param_iter_update(self, grad_iter):
         if self.mean.grad is not None:
             self.mean_grads_norm += self.mean.grad.norm(dim=1)
@@ -492,8 +225,7 @@ class GS_model_with_param(torch.nn.Module):
 
     def _replace(self, keep, extra=None):
         """Keep rows `keep` of every per-Gaussian tensor and append `extra` (dict name -> rows)."""
-        names = ("mean", "variance_q", "variance_scale", "opacity", "color")
-        for name in names:
+        for name in PARAM_NAMES:
             rows = getattr(self, name).data[keep]
             if extra is not None:
                 rows = torch.cat((rows, extra[name]), dim=0)
@@ -506,7 +238,7 @@ class GS_model_with_param(torch.nn.Module):
 
     def _rows(self, mask, repeat=1):
         out = {k: getattr(self, k).data[mask].repeat(repeat, *([1] * (getattr(self, k).dim() - 1)))
-               for k in ("mean", "variance_q", "variance_scale", "opacity", "color")}
+               for k in PARAM_NAMES}
         out["mean_grads_norm"] = self.mean_grads_norm[mask].repeat(repeat)
         out["mean_grads_iter"] = self.mean_grads_iter[mask].repeat(repeat)
         return out
@@ -579,56 +311,21 @@ class GS_model_with_param(torch.nn.Module):
             raise RuntimeError("density control on the device is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("densify_and_prune_device reads the new row count back: it cannot be captured into a graph")
-        names = ("mean", "variance_q", "variance_scale", "opacity", "color")
-        old = {k: getattr(self, k) for k in names}
-        src = {k: old[k].data.contiguous() for k in names}
-        dev, n = self.mean.device, self.mean.shape[0]
+        old = {k: getattr(self, k) for k in PARAM_NAMES}
+        n = self.mean.shape[0]
         norm, views = (t.contiguous() for t in self._density_stats())
         if norm.numel() != n or views.numel() != n:  # the active pair only: the other one is reallocated below
             raise RuntimeError("the densification statistic does not have one row per Gaussian")
-        lib = _lib.load()
-        count, offset = (torch.empty(k, dtype=torch.int32, device=dev) for k in (n, n + 1))
-        action = torch.empty(n, dtype=torch.uint8, device=dev)
-        ws = torch.empty(lib.gcp_densify_plan_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        seed = int(seed) & (2 ** 64 - 1)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.gcp_densify_plan(norm.data_ptr(), views.data_ptr(), src["variance_scale"].data_ptr(), src["opacity"].data_ptr(), n,
-                                            float(self.grad_threshold), float(self.percent_dense * extent), float(0.1 * extent),
-                                            float(self.prunning_min_opacity), int(n_split), count.data_ptr(), action.data_ptr(),
-                                            offset.data_ptr(), ws.data_ptr(), ws.numel(), stream), "gcp_densify_plan")
-            m = int(offset[n])  # the one device->host read
-            src_row = torch.empty(m, dtype=torch.int32, device=dev)
-            kind = torch.empty(m, dtype=torch.uint8, device=dev)
-            _lib.check(lib.gcp_densify_fill(action.data_ptr(), offset.data_ptr(), n, m, src_row.data_ptr(), kind.data_ptr(), stream),
-                       "gcp_densify_fill")
-
-            def rows(t, mode):
-                out = torch.empty((m, *t.shape[1:]), dtype=torch.float32, device=dev)
-                _lib.check(lib.gcp_densify_rows(t.data_ptr(), n, src_row.data_ptr(), kind.data_ptr(), m, t[0].numel() if n else 0, mode,
-                                                out.data_ptr(), stream), "gcp_densify_rows")
-                return out
-
-            new = {k: rows(src[k], 0) for k in names}
-            _lib.check(lib.gcp_densify_split(src["mean"].data_ptr(), src["variance_q"].data_ptr(), src["variance_scale"].data_ptr(),
-                                             src_row.data_ptr(), kind.data_ptr(), offset.data_ptr(), n, m, int(n_split), seed & 0xFFFFFFFF,
-                                             seed >> 32, new["mean"].data_ptr(), new["variance_scale"].data_ptr(), stream),
-                       "gcp_densify_split")
-            state = {}
-            for k in names:
-                st = self._optimizer.state.get(old[k])
-                if st:
-                    state[k] = {"step": st["step"], "exp_avg": rows(st["exp_avg"].contiguous(), 1),
-                                "exp_avg_sq": rows(st["exp_avg_sq"].contiguous(), 1)}
-        for k in names:
+        states = {k: st for k, st in ((k, self._optimizer.state.get(p)) for k, p in old.items()) if st}
+        new, moments, m = density.densify_rows(
+            {k: p.data.contiguous() for k, p in old.items()}, {k: (st["exp_avg"], st["exp_avg_sq"]) for k, st in states.items()},
+            norm, views, self.grad_threshold, self.percent_dense * extent, 0.1 * extent, self.prunning_min_opacity, n_split, seed)
+        for k in PARAM_NAMES:
             setattr(self, k, torch.nn.Parameter(new[k]))
         self.changing_optimizer()
-        for k, st in state.items():
-            self._optimizer.state[getattr(self, k)] = st
-        self.mean_grads_norm = torch.zeros(m, device=dev, dtype=torch.float32)
-        self.mean_grads_iter = torch.zeros(m, device=dev, dtype=torch.int16)
-        self.screen_grads_norm = torch.zeros(m, device=dev, dtype=torch.float32)
-        self.screen_grads_views = torch.zeros(m, device=dev, dtype=torch.int32)
+        for k, (exp_avg, exp_avg_sq) in moments.items():
+            self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        self._zero_density_stats(m)
         return n, m
 
     def allreduce_density_stats(self, group=None):
@@ -703,21 +400,32 @@ class GS_model_with_param(torch.nn.Module):
             model.color.copy_(color)
         return model
 
+    @staticmethod
+    def _draw_cameras(cams, names, draw):
+        """`draw(cam)`, a tuple of maps, for every camera that sees anything (the reference drops the others from the batch,
+        :414-417) -> (every map stacked over those cameras, their names)."""
+        drawn, kept = [], []
+        for cam, name in zip(cams, names):
+            if cam is None:
+                continue
+            drawn.append(draw(cam))
+            kept.append(name)
+        if not drawn:
+            raise RuntimeError("no camera of the batch sees any Gaussian")  # the reference fails in torch.stack (:454)
+        return [torch.stack(maps, dim=0) for maps in zip(*drawn)], kept
+
     def forward(self, P, K, wh, image_sample):
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh)
         self._watch_centres(cams, width, height)
-        images, names = [], []
-        for cam, name in zip(cams, image_sample):
-            if cam is None:
-                continue  # nothing visible: the reference drops the image from the batch (:414-417)
+
+        def draw(cam):
             batch = cam["boxsize"].new_tensor([cam["boxsize"].numel()])
-            images.append(custom_autograd_grouped_cumprod.apply(
+            return (custom_autograd_grouped_cumprod.apply(
                 cam["boxsize"], batch, cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"],
-                cam["opacity"], cam["l_d"], width, height))
-            names.append(name)
-        if not images:
-            raise RuntimeError("no camera of the batch sees any Gaussian")  # the reference fails in torch.stack (:454)
-        out = torch.stack(images, dim=0)[:, 1:, 1:, :]
+                cam["opacity"], cam["l_d"], width, height),)
+
+        (out,), names = self._draw_cameras(cams, image_sample, draw)
+        out = out[:, 1:, 1:, :]
         h, w = int(height), int(width)
         out = out.reshape(-1, 3, h, w) if self.reference_layout else out.permute(0, 3, 1, 2).contiguous()
         return [out, names, grad_iter]
@@ -731,84 +439,11 @@ class GS_model_with_param(torch.nn.Module):
         cameras that see anything — the others are dropped, as in `forward`."""
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
         self._watch_centres(cams, width, height)
-        names_in = list(range(P.shape[0])) if image_sample is None else image_sample
-        images, depths, alphas, names = [], [], [], []
-        for cam, name in zip(cams, names_in):
-            if cam is None:
-                continue
-            img, dep, alp = render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
-                                   cam["l_d"], cam["depth"], width, height, background)
-            images.append(img)
-            depths.append(dep)
-            alphas.append(alp)
-            names.append(name)
-        if not images:
-            raise RuntimeError("no camera of the batch sees any Gaussian")
-        images = torch.stack(images)[:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
-        depth = torch.stack(depths)[:, None, 1:, 1:].contiguous()
-        alpha = torch.stack(alphas)[:, None, 1:, 1:].contiguous()
+        (images, depth, alpha), names = self._draw_cameras(
+            cams, range(P.shape[0]) if image_sample is None else image_sample,
+            lambda cam: render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
+                               cam["depth"], width, height, background))
+        images = images[:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
+        depth = depth[:, None, 1:, 1:].contiguous()
+        alpha = alpha[:, None, 1:, 1:].contiguous()
         return [images, depth, alpha, names, grad_iter]
-
-
-_WINDOW_CACHE = {}
-
-
-def _host_window(window_size, sigma):
-    """The normalised window as a ctypes float array (host memory, handed to the loss kernels by value)."""
-    import ctypes
-
-    key = (window_size, sigma)
-    if key not in _WINDOW_CACHE:
-        x = torch.arange(window_size, dtype=torch.float32) - (window_size - 1) / 2
-        w = torch.exp(-(x * x) / (2 * sigma * sigma))
-        _WINDOW_CACHE[key] = (ctypes.c_float * window_size)(*(w / w.sum()).tolist())
-    return _WINDOW_CACHE[key]
-
-
-class _SplatLoss(torch.autograd.Function):
-    """(1 - lambda) L1 + lambda (1 - mean SSIM) in one HIP kernel per direction (csrc/gcp_loss.hip); differentiable in
-    the first image only (the second is the target photograph)."""
-
-    @staticmethod
-    def forward(ctx, images, targets, lamda, max_val):
-        if not images.is_cuda:
-            raise RuntimeError("the fused loss is a HIP kernel: tensors must live on the GPU (no CPU path)")
-        if images.shape != targets.shape or images.dim() != 4:
-            raise RuntimeError("splat_loss expects two (B, C, H, W) tensors of one shape")
-        a, b = images.detach().contiguous().float(), targets.detach().contiguous().float()
-        bsz, ch, h, w = a.shape
-        lib = _lib.load()
-        win = _host_window(11, 1.5)
-        need_grad = images.requires_grad
-        maps = [torch.empty_like(a) for _ in range(3)] if need_grad else [None] * 3
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            partial = torch.empty(lib.gcp_ssim_blocks(bsz * ch, h, w), 2, dtype=torch.float32, device=a.device)
-            _lib.check(lib.gcp_ssim_l1_forward(a.data_ptr(), b.data_ptr(), bsz * ch, h, w, win, (0.01 * max_val) ** 2,
-                                               (0.03 * max_val) ** 2, *(m.data_ptr() if need_grad else None for m in maps),
-                                               partial.data_ptr(), stream), "gcp_ssim_l1_forward")
-        sums = partial.double().sum(dim=0) / a.numel()  # [mean SSIM, mean |a - b|]
-        ctx.save_for_backward(a, b, *(maps if need_grad else []))
-        ctx.lamda, ctx.dtype = lamda, images.dtype
-        return ((1 - lamda) * sums[1] + lamda * (1 - sums[0])).to(images.dtype)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        a, b, m1, m2, m3 = ctx.saved_tensors
-        n = a.numel()
-        scales = (grad_out.reshape(1).float() * torch.tensor([-ctx.lamda / n, (1 - ctx.lamda) / n], device=a.device)).contiguous()
-        grad = torch.empty_like(a)
-        bsz, ch, h, w = a.shape
-        with torch.cuda.device(a.device):
-            stream = torch.cuda.current_stream(a.device).cuda_stream
-            _lib.check(_lib.load().gcp_ssim_l1_backward(a.data_ptr(), b.data_ptr(), m1.data_ptr(), m2.data_ptr(), m3.data_ptr(), bsz * ch,
-                                                        h, w, _host_window(11, 1.5), scales.data_ptr(), grad.data_ptr(), stream),
-                       "gcp_ssim_l1_backward")
-        return grad.to(ctx.dtype), None, None, None
-
-
-def splat_loss(images, targets, lamda=0.2):
-    """(1 - lambda) L1 + lambda (1 - mean SSIM), 11-tap Gaussian window, reflect padding (reference:
-    gs_control.py:180-182, kornia.metrics.ssim).  Both terms and their gradient are one HIP kernel per direction
-    (csrc/gcp_loss.hip); GPU tensors only.  The PyTorch formulation it is tested against: oracle/loss_torch.py."""
-    return _SplatLoss.apply(images, targets, float(lamda), 1.0)
