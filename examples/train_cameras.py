@@ -21,6 +21,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --centres subpixel --densify device --densify-on screen
                                                              # split / clone / prune in one pass of HIP kernels that keeps Adam's
                                                              # moments, decided on the screen-space gradient of the centres
+    python examples/train_cameras.py --densify mcmc --cap-max 4000
+                                                             # the MCMC strategy: dead Gaussians relocated onto live ones, 5 % more
+                                                             # rows per pass up to the cap, position noise after every step
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -82,7 +85,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           densify_from_iter=500, densify_until_iter=15000, densification_interval=100, opacity_reset_interval=3000,
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
-          densify="reference", densify_on="position", antialias=False):
+          densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -96,9 +99,13 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `densify`: "reference" (the default: `densify_and_prune` / `reset_opacity`, which rebuild Adam without its moments, split
     samples from torch's generator) or "device" (`densify_and_prune_device` with seed + iteration and
     `reset_opacity(keep_optimizer=True)`: one pass of HIP kernels, Adam's state kept, the statistic summed over the ranks
-    first).  `densify_on`: the statistic the device path decides on, "position" or "screen" (GS_model_with_param)."""
-    if densify not in ("reference", "device"):
-        raise ValueError(f"densify: 'reference' or 'device', got {densify!r}")
+    first) or "mcmc" (3DGS-MCMC: the loss gains opacity_reg * mean sigmoid(opacity) + scale_reg * mean exp(variance_scale),
+    `add_position_noise(seed + iteration, noise_lr)` follows every optimiser step, and on the densification schedule
+    `relocate_and_grow_device(seed + iteration, cap_max)` relocates the dead Gaussians and grows the scene by 5 % up to
+    `cap_max` (None: no growth); no opacity reset and no statistic: every rank draws the same samples from the same
+    parameters).  `densify_on`: the statistic the device path decides on, "position" or "screen" (GS_model_with_param)."""
+    if densify not in ("reference", "device", "mcmc"):
+        raise ValueError(f"densify: 'reference', 'device' or 'mcmc', got {densify!r}")
     if isinstance(background, str) and background != "random":
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
@@ -140,6 +147,9 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     if target_alpha is not None:
                         target = target + (1 - target_alpha[sel]) * bg[None, :, None, None]
                 loss = gm.splat_loss(images, target, loss_lamda) * (mine.numel() / idx.numel())
+                if densify == "mcmc":  # the regularisers that let opacities die and keep scales small; the whole term on every rank's share
+                    loss = loss + (opacity_reg * torch.sigmoid(model.opacity).mean()
+                                   + scale_reg * torch.exp(model.variance_scale).mean()) * (mine.numel() / idx.numel())
                 loss.backward()
             else:  # more ranks than cameras in this batch
                 loss, grad_iter = torch.zeros((), device=dev), torch.zeros(model.mean.shape[0], dtype=torch.bool, device=dev)
@@ -154,19 +164,23 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     torch.distributed.all_reduce(loss)
             model.param_iter_update(grad_iter)
             model.train_step()
+            if densify == "mcmc":
+                model.add_position_noise(seed + iteration, noise_lr)
             iteration += 1
             losses.append(float(loss.detach()))
             model.set_mean_lr(iteration)
             if sh_every and iteration % sh_every == 0:
                 model.oneup_sh_degree()
             if densify_from_iter <= iteration <= densify_until_iter and iteration % densification_interval == 0:
-                if densify == "device":
+                if densify == "mcmc":
+                    model.relocate_and_grow_device(seed + iteration, cap_max)
+                elif densify == "device":
                     if world > 1:
                         model.allreduce_density_stats()
                     model.densify_and_prune_device(extent, seed=seed + iteration)
                 else:
                     model.densify_and_prune(extent)
-            if opacity_reset_interval and iteration % opacity_reset_interval == 0:
+            if opacity_reset_interval and iteration % opacity_reset_interval == 0 and densify != "mcmc":
                 if densify == "device":
                     model.reset_opacity(reset_opacity_min, keep_optimizer=True)
                 else:
@@ -207,8 +221,13 @@ if __name__ == "__main__":
     ap.add_argument("--clamp-colour", action="store_true", help="clamp the SH colour at 0")
     ap.add_argument("--antialias", action="store_true",
                     help="scale each opacity by sqrt(det Sigma / det Sigma'), the energy the dilation adds (needs --dilation > 0)")
-    ap.add_argument("--densify", choices=("reference", "device"), default="reference",
-                    help="device = split / clone / prune in one pass of HIP kernels that keeps Adam's moments; reference = the reference's")
+    ap.add_argument("--densify", choices=("reference", "device", "mcmc"), default="reference",
+                    help="device = split / clone / prune in one pass of HIP kernels that keeps Adam's moments; reference = the reference's; "
+                         "mcmc = relocate dead Gaussians, grow to --cap-max, position noise after every step (3DGS-MCMC)")
+    ap.add_argument("--cap-max", type=int, default=None, metavar="N", help="--densify mcmc: grow by 5 %% per pass up to N Gaussians (default: no growth)")
+    ap.add_argument("--noise-lr", type=float, default=5e5, help="--densify mcmc: the position noise is lr_mean * this * gate * Sigma z")
+    ap.add_argument("--opacity-reg", type=float, default=0.01, help="--densify mcmc: weight of mean sigmoid(opacity) in the loss")
+    ap.add_argument("--scale-reg", type=float, default=0.01, help="--densify mcmc: weight of mean exp(variance_scale) in the loss")
     ap.add_argument("--densify-on", choices=("position", "screen"), default="position",
                     help="statistic of --densify device: screen = gradient of the 2-D centres per view (needs --centres subpixel)")
     a = ap.parse_args()
@@ -234,7 +253,7 @@ if __name__ == "__main__":
                       log=print if rank == 0 else (lambda *_: None), background=background, target_alpha=alphas, sh_degree=a.sh_degree,
                       sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply, centres=a.centres,
                       dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on,
-                      antialias=a.antialias)
+                      antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

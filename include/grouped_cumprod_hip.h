@@ -735,6 +735,50 @@ int gcp_densify_split(const float* mean, const float* quat_xyzw, const float* lo
                       const int32_t* offset, int64_t n_gauss, int64_t n_rows, int32_t n_split, uint32_t seed_lo, uint32_t seed_hi,
                       float* mean_out, float* log_scale_out, void* stream);
 
+/* ---- MCMC density control on the device (3DGS-MCMC, Kheradmand et al., NeurIPS 2024; csrc/gcp_mcmc.hip) -------------
+ * Dead Gaussians are relocated onto live ones drawn with probability proportional to opacity, the scene grows to a row
+ * count the HOST fixes, and a small opacity-gated noise moves the positions after every optimiser step.  No gradient
+ * statistic, no threshold and no device->host read: n_rows is the caller's arithmetic, the total weight is read from
+ * cum[n_gauss] on the device, and no entry point waits for the stream.  n_gauss = rows before the pass, n_rows >= n_gauss
+ * rows after it; a SLOT is an output row r that draws a source: r >= n_gauss, or r < n_gauss and dead.  Every entry point
+ * validates before any HIP call (a negative size, n_rows < n_gauss, n_gauss == 0 with n_rows > 0, n_rows > INT32_MAX,
+ * n_gauss * w_max > INT32_MAX, w_max not a power of two in [1, 2^16], NULL with rows to process, a non-finite
+ * min_opacity, amount, k or o0: GCP_ERR_INVALID_ARGUMENT); n_gauss == 0 (then n_rows == 0) is a no-op that touches
+ * nothing.  The one atomic counts draws in an integer: results are bit-identical whatever the launch shape.
+ *
+ * gcp_mcmc_weights: o = sigmoid(opacity_logit) in float32; dead = !(o > min_opacity) (NaN is dead);
+ * weight[i] = dead ? 0 : clamp((int)floorf(o * w_max), 1, w_max); cum[n_gauss + 1] = the exclusive prefix sum of weight,
+ * cum[n_gauss] = T.  w_max: the caller passes the largest power of two <= 2^16 with n_gauss * w_max <= INT32_MAX, so
+ * the draw is an exact integer one at 2^16 levels up to 32 767 Gaussians and 2^11 levels at 10^6.
+ * ws: gcp_mcmc_workspace_bytes(n_gauss) bytes.
+ *
+ * gcp_mcmc_draw: zeroes times[n_gauss], then for every output row r < n_rows: a slot runs Philox4x32-10 with key
+ * (seed_lo, seed_hi) and counter (r, 0, 0, 2), t = ((uint64)out[0] * T) >> 32, src_row[r] = the s with
+ * cum[s] <= t < cum[s + 1] (an upper bound by binary search over cum[1..n_gauss]; never a dead row), times[s] += 1;
+ * every other row gets src_row[r] = r.  T == 0 (everything dead): src_row[r] = r mod n_gauss, times stays 0.  Then
+ * kind[r] = 0 (survivor: gcp_densify_rows mode 1 carries its moments) iff r < n_gauss && src_row[r] == r &&
+ * times[r] == 0, else 1 (fresh: moments 0.0).  The rows themselves are gathered with gcp_densify_rows.
+ *
+ * gcp_mcmc_values: for every output row r with p = src_row[r], c = times[p] > 0 and n = min(c + 1, 51), in float64 from
+ * the arrays BEFORE the pass (n_gauss rows): o = sigmoid(opacity_logit[p]), o' = 1 - (1 - o)^(1/n),
+ *     D = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1),
+ * log_scale_out[r, :] = (float)(log_scale[p, :] + log(o / D)), opacity_out[r] = (float)logit(clamp(o', min_opacity,
+ * 1 - 2^-23)): the source and every slot that drew it receive the same values.  Rows with c == 0 are not touched.
+ *
+ * gcp_mcmc_noise: in place on mean f32[n_gauss, 3], float32: o = sigmoid(opacity_logit), gate = 1 / (1 + expf(-k (o0 - o))),
+ * z = the three normals of gcp_densify_split's mapping from Philox counter (i, 0, 0, 1), R = R(q / max(|q|, 1e-8)),
+ * s = exp(log_scale): mean[i] += amount * gate * R (s^2 (.) (R^T z)).  quat_xyzw 16-byte aligned (rows are read whole).
+ * 44 bytes read and 12 written per Gaussian. */
+size_t gcp_mcmc_workspace_bytes(int64_t n_gauss);
+int gcp_mcmc_weights(const float* opacity_logit, int64_t n_gauss, float min_opacity, int32_t w_max, int32_t* weight, int32_t* cum,
+                     void* ws, size_t ws_bytes, void* stream);
+int gcp_mcmc_draw(const int32_t* cum, int64_t n_gauss, int64_t n_rows, uint32_t seed_lo, uint32_t seed_hi, int32_t* src_row,
+                  int32_t* times, uint8_t* kind, void* stream);
+int gcp_mcmc_values(const float* opacity_logit, const float* log_scale, const int32_t* src_row, const int32_t* times, int64_t n_gauss,
+                    int64_t n_rows, float min_opacity, float* opacity_out, float* log_scale_out, void* stream);
+int gcp_mcmc_noise(float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit, int64_t n_gauss,
+                   float amount, float k, float o0, uint32_t seed_lo, uint32_t seed_hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

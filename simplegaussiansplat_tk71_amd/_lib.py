@@ -132,6 +132,12 @@ SIGNATURES = {
     "gcp_densify_fill": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
     "gcp_densify_rows": (ctypes.c_int, [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
     "gcp_densify_split": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i64, _i32, ctypes.c_uint32, ctypes.c_uint32] + [_c_void_p] * 3),
+    # MCMC density control (gcp_mcmc.hip): weights and their prefix sum, draw (src_row, times, kind), relocated values, position noise
+    "gcp_mcmc_workspace_bytes": (_sz, [_i64]),
+    "gcp_mcmc_weights": (ctypes.c_int, [_c_void_p, _i64, ctypes.c_float, _i32, _c_void_p, _c_void_p, _c_void_p, _sz, _c_void_p]),
+    "gcp_mcmc_draw": (ctypes.c_int, [_c_void_p, _i64, _i64, ctypes.c_uint32, ctypes.c_uint32] + [_c_void_p] * 4),
+    "gcp_mcmc_values": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i64, ctypes.c_float] + [_c_void_p] * 3),
+    "gcp_mcmc_noise": (ctypes.c_int, [_c_void_p] * 4 + [_i64] + [ctypes.c_float] * 3 + [ctypes.c_uint32, ctypes.c_uint32, _c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -12,6 +12,7 @@
 // offset[N] (4 bytes).
 #include <math.h>
 
+#include "gcp_philox.hpp"
 #include "gcp_tiles.hpp"
 
 namespace {
@@ -128,25 +129,6 @@ __global__ __launch_bounds__(kThreads) void k_densify_rows(const float* __restri
   }
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1, c3 = (unsigned)p0, c0 = n0, c2 = n2;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
-}
-
-__device__ __forceinline__ float unit_open(unsigned r) { return ((float)r + 0.5f) * 2.3283064365386963e-10f; }  // (r + 0.5) 2^-32, in (0, 1]
-
-// ln u of u = (r + 0.5) 2^-32 to float accuracy over the whole range: the float u has 24 bits, so above 1/2 — where ln u
-// goes to 0 and the radius sqrt(-2 ln u) with it — the logarithm is taken from 1 - u = (~r + 0.5) 2^-32, which is exact
-// where u is not (r = 2^32 - 1 gives ln u = -1.16e-10, not 0).
-__device__ __forceinline__ float log_unit_open(unsigned r) { return r < 0x80000000u ? logf(unit_open(r)) : log1pf(-unit_open(~r)); }
-
 // One thread per output row; only split children do anything.  The child number is the row's place among its parent's
 // rows (they are contiguous): r - offset[parent].  Every draw depends on (seed, parent, child) alone.
 __global__ __launch_bounds__(kThreads) void k_densify_split(const float* __restrict__ mean, const float* __restrict__ quat,
@@ -160,24 +142,19 @@ __global__ __launch_bounds__(kThreads) void k_densify_split(const float* __restr
     if (p < 0 || p >= N) continue;
     const unsigned child = (unsigned)((int)r - offset[p]);
     unsigned rnd[4];
-    philox4x32_10((unsigned)p, child, 0u, 0u, seed_lo, seed_hi, rnd);
-    const float ra = sqrtf(-2.0f * log_unit_open(rnd[0])), rb = sqrtf(-2.0f * log_unit_open(rnd[2]));
+    gcp::philox4x32_10((unsigned)p, child, 0u, 0u, seed_lo, seed_hi, rnd);
+    const float ra = sqrtf(-2.0f * gcp::log_unit_open(rnd[0])), rb = sqrtf(-2.0f * gcp::log_unit_open(rnd[2]));
     float sa, ca, sb, cb;
-    sincosf(6.283185307179586f * unit_open(rnd[1]), &sa, &ca);
-    sincosf(6.283185307179586f * unit_open(rnd[3]), &sb, &cb);
+    sincosf(6.283185307179586f * gcp::unit_open(rnd[1]), &sa, &ca);
+    sincosf(6.283185307179586f * gcp::unit_open(rnd[3]), &sb, &cb);
     (void)sb;
     const float sx = expf(log_scale[3 * p]), sy = expf(log_scale[3 * p + 1]), sz = expf(log_scale[3 * p + 2]);
     const float vx = sx * (ra * ca), vy = sy * (ra * sa), vz = sz * (rb * cb);  // sigma (.) z
-    float x = quat[4 * p], y = quat[4 * p + 1], z = quat[4 * p + 2], w = quat[4 * p + 3];
-    const float inv = 1.0f / fmaxf(sqrtf(x * x + y * y + z * z + w * w), 1e-8f);
-    x *= inv, y *= inv, z *= inv, w *= inv;
-    // qvec_to_rotmat_batch, (x, y, z, w)
-    const float r00 = 1 - 2 * (y * y + z * z), r01 = 2 * (x * y - w * z), r02 = 2 * (x * z + w * y);
-    const float r10 = 2 * (x * y + w * z), r11 = 1 - 2 * (x * x + z * z), r12 = 2 * (y * z - w * x);
-    const float r20 = 2 * (x * z - w * y), r21 = 2 * (y * z + w * x), r22 = 1 - 2 * (x * x + y * y);
-    mean_out[3 * r] = mean[3 * p] + (r00 * vx + r01 * vy + r02 * vz);
-    mean_out[3 * r + 1] = mean[3 * p + 1] + (r10 * vx + r11 * vy + r12 * vz);
-    mean_out[3 * r + 2] = mean[3 * p + 2] + (r20 * vx + r21 * vy + r22 * vz);
+    float rot[9];
+    gcp::quat_rotation(quat[4 * p], quat[4 * p + 1], quat[4 * p + 2], quat[4 * p + 3], rot);
+    mean_out[3 * r] = mean[3 * p] + (rot[0] * vx + rot[1] * vy + rot[2] * vz);
+    mean_out[3 * r + 1] = mean[3 * p + 1] + (rot[3] * vx + rot[4] * vy + rot[5] * vz);
+    mean_out[3 * r + 2] = mean[3 * p + 2] + (rot[6] * vx + rot[7] * vy + rot[8] * vz);
     log_scale_out[3 * r] = logf(sx / child_div);
     log_scale_out[3 * r + 1] = logf(sy / child_div);
     log_scale_out[3 * r + 2] = logf(sz / child_div);

@@ -1,6 +1,7 @@
-"""Density control on the device (csrc/gcp_densify.hip): the screen-space statistic and the kernel sequence of the
-one-pass split / clone / prune.  What belongs to the model — parameters, optimiser, statistics — stays in
-`GS_model_with_param.densify_and_prune_device`."""
+"""Density control on the device: the screen-space statistic and the kernel sequence of the one-pass split / clone / prune
+(csrc/gcp_densify.hip), and the MCMC strategy's relocation pass and position noise (csrc/gcp_mcmc.hip).  What belongs to
+the model — parameters, optimiser, statistics — stays in `GS_model_with_param.densify_and_prune_device` and
+`relocate_and_grow_device`."""
 import torch
 
 from . import _lib
@@ -76,3 +77,72 @@ def densify_rows(params, moments, norm, views, grad_threshold, split_scale, prun
                    "gcp_densify_split")
         new_moments = {k: tuple(rows(t.contiguous(), 1) for t in pair) for k, pair in moments.items()}
     return new, new_moments, m
+
+
+def mcmc_weight_levels(n):
+    """W of gcp_mcmc_weights: the largest power of two <= 2^16 with n * W <= 2^31 - 1 (the prefix sum is int32)."""
+    w = 1 << 16
+    while w > 1 and n * w > 2 ** 31 - 1:
+        w >>= 1
+    return w
+
+
+def mcmc_noise(mean, variance_q, variance_scale, opacity, amount, seed, k=100.0, o0=0.005):
+    """The MCMC strategy's position noise (gcp_mcmc_noise, csrc/gcp_mcmc.hip), in place on `mean` float32 (N, 3):
+    mean += amount * gate * R (s^2 (.) (R^T z)), gate = 1 / (1 + exp(-k (o0 - sigmoid(opacity)))), R from variance_q (x, y, z, w)
+    normalised, s = exp(variance_scale), z standard normal from Philox4x32-10 keyed by `seed` (64 bits), counter (i, 0, 0, 1).
+    Contiguous float32 GPU tensors only."""
+    tensors = (mean, variance_q, variance_scale, opacity)
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("the position noise is a HIP kernel: tensors must live on the GPU (no CPU path)")
+    n = mean.shape[0]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise RuntimeError("mcmc_noise expects contiguous float32 tensors")
+    if tuple(mean.shape) != (n, 3) or tuple(variance_q.shape) != (n, 4) or tuple(variance_scale.shape) != (n, 3) or opacity.numel() != n:
+        raise RuntimeError("mcmc_noise expects mean (N, 3), variance_q (N, 4), variance_scale (N, 3) and opacity (N, 1)")
+    seed = int(seed) & (2 ** 64 - 1)
+    with torch.cuda.device(mean.device):
+        _lib.check(_lib.load().gcp_mcmc_noise(mean.data_ptr(), variance_q.data_ptr(), variance_scale.data_ptr(), opacity.data_ptr(), n,
+                                              float(amount), float(k), float(o0), seed & 0xFFFFFFFF, seed >> 32,
+                                              torch.cuda.current_stream(mean.device).cuda_stream), "gcp_mcmc_noise")
+
+
+def mcmc_rows(params, moments, n_out, min_opacity, seed):
+    """The kernel sequence of `GS_model_with_param.relocate_and_grow_device`, whose docstring states the rule: weights (an
+    integer weight per Gaussian, 0 when dead, and their prefix sum), draw (every new row and every dead row draws a live
+    source; how often each source was drawn; survivor or fresh), the row gathers of `densify_rows`, values (opacity and
+    scale of the sources that were drawn and of their copies).  No device->host read anywhere: n_out is the caller's.
+    params, moments: as `densify_rows`; n_out >= n rows come out; a Gaussian is dead at !(sigmoid(opacity) > min_opacity);
+    seed: 64 bits.
+    -> (new params by name, new (exp_avg, exp_avg_sq) by name — rows that were drawn from, or written by a draw, 0.0 —,
+        {"src_row" int32 (n_out,), "kind" uint8 (n_out,), "times" int32 (n,), "cum" int32 (n + 1,), "weight" int32 (n,)})"""
+    if not all(t.is_cuda for t in params.values()):
+        raise RuntimeError("the relocation pass is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
+    dev, n, m = params["mean"].device, params["mean"].shape[0], int(n_out)
+    if m < n or (n == 0 and m > 0):
+        raise RuntimeError(f"mcmc_rows: {n} rows cannot become {m} (rows are never dropped, and nothing grows out of nothing)")
+    lib = _lib.load()
+    weight, times, src_row = (torch.empty(k, dtype=torch.int32, device=dev) for k in (n, n, m))
+    cum = torch.zeros(n + 1, dtype=torch.int32, device=dev)  # zeros: with n == 0 the entry points touch nothing
+    kind = torch.empty(m, dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.gcp_mcmc_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    seed = int(seed) & (2 ** 64 - 1)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.gcp_mcmc_weights(params["opacity"].data_ptr(), n, float(min_opacity), mcmc_weight_levels(n), weight.data_ptr(),
+                                        cum.data_ptr(), ws.data_ptr(), ws.numel(), stream), "gcp_mcmc_weights")
+        _lib.check(lib.gcp_mcmc_draw(cum.data_ptr(), n, m, seed & 0xFFFFFFFF, seed >> 32, src_row.data_ptr(), times.data_ptr(),
+                                     kind.data_ptr(), stream), "gcp_mcmc_draw")
+
+        def rows(t, mode):
+            out = torch.empty((m, *t.shape[1:]), dtype=torch.float32, device=dev)
+            _lib.check(lib.gcp_densify_rows(t.data_ptr(), n, src_row.data_ptr(), kind.data_ptr(), m, t[0].numel() if n else 0, mode,
+                                            out.data_ptr(), stream), "gcp_densify_rows")
+            return out
+
+        new = {k: rows(t, 0) for k, t in params.items()}
+        _lib.check(lib.gcp_mcmc_values(params["opacity"].data_ptr(), params["variance_scale"].data_ptr(), src_row.data_ptr(), times.data_ptr(),
+                                       n, m, float(min_opacity), new["opacity"].data_ptr(), new["variance_scale"].data_ptr(), stream),
+                   "gcp_mcmc_values")
+        new_moments = {k: tuple(rows(t.contiguous(), 1) for t in pair) for k, pair in moments.items()}
+    return new, new_moments, {"src_row": src_row, "kind": kind, "times": times, "cum": cum, "weight": weight}

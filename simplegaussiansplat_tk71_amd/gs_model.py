@@ -328,6 +328,51 @@ class GS_model_with_param(torch.nn.Module):
         self._zero_density_stats(m)
         return n, m
 
+    # ---- the MCMC strategy (3DGS-MCMC, Kheradmand et al. 2024; csrc/gcp_mcmc.hip) -----------------------------------------
+    @torch.no_grad()
+    def add_position_noise(self, seed, noise_lr=5e5):
+        """After an optimiser step: mean += lr_mean * noise_lr * gate * Sigma z, in place, one HIP kernel (`density.mcmc_noise`).
+        gate = sigmoid(100 (0.005 - sigmoid(opacity))) lets only nearly transparent Gaussians move, Sigma is the Gaussian's own
+        covariance, z a Philox4x32-10 normal keyed by `seed` (64 bits) and counted by the Gaussian: the same on every rank.
+        lr_mean is `self.lr["mean"]`, the rate `set_mean_lr` keeps.  GPU only."""
+        density.mcmc_noise(self.mean.data, self.variance_q.data, self.variance_scale.data, self.opacity.data,
+                           float(self.lr["mean"]) * noise_lr, seed)
+
+    @torch.no_grad()
+    def relocate_and_grow_device(self, seed, cap_max=None, growth=1.05, min_opacity=None):
+        """Relocate dead Gaussians and grow the scene to a fixed row count in ONE pass of HIP kernels that keeps Adam's
+        state; returns (n_before, n_after).  n_after = n_before when `cap_max` is None, else
+        max(n_before, min(cap_max, int(growth * n_before))): host arithmetic, so the pass reads nothing back from the device
+        and needs no gradient statistic, no threshold and no opacity reset.
+
+        A Gaussian is dead at !(sigmoid(opacity) > min_opacity) (default `prunning_min_opacity`; the raw opacity, also under
+        antialias=True).  Every dead row and every new row is a slot that draws a live source with probability proportional to its
+        opacity (integer weights of 2^16 levels, fewer above 32 767 Gaussians: DESIGN.md §5) from Philox4x32-10 keyed by `seed`
+        (64 bits) and counted by the row: the same on every rank.  A slot becomes a copy of its source; a source drawn c times
+        and its c copies all get the opacity o' with (1 - o')^(c + 1) = 1 - o and the scale that keeps what the source rendered
+        (the paper's relocation rule, c + 1 capped at 51), computed in float64.  Rows that nothing drew are untouched.
+        Two deviations from the published code.  One pass on the state before it instead of relocate-then-add: both kinds
+        of slot draw from the same distribution, and a source's count is the sum over both.  And Adam's moments are zeroed on
+        relocated rows as well as on their sources; the published code zeroes only the sources' and leaves a relocated row
+        the moments of the Gaussian it replaced.  Every other row keeps exp_avg / exp_avg_sq, every tensor's `step` is kept.
+        All statistic arrays come back zeroed at the new length.  GPU only."""
+        if not self.mean.is_cuda:
+            raise RuntimeError("density control on the device is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
+        old = {k: getattr(self, k) for k in PARAM_NAMES}
+        n = self.mean.shape[0]
+        m = n if cap_max is None else max(n, min(int(cap_max), int(growth * n)))
+        states = {k: st for k, st in ((k, self._optimizer.state.get(p)) for k, p in old.items()) if st}
+        new, moments, _ = density.mcmc_rows(
+            {k: p.data.contiguous() for k, p in old.items()}, {k: (st["exp_avg"], st["exp_avg_sq"]) for k, st in states.items()},
+            m, self.prunning_min_opacity if min_opacity is None else min_opacity, seed)
+        for k in PARAM_NAMES:
+            setattr(self, k, torch.nn.Parameter(new[k]))
+        self.changing_optimizer()
+        for k, (exp_avg, exp_avg_sq) in moments.items():
+            self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        self._zero_density_stats(m)
+        return n, m
+
     def allreduce_density_stats(self, group=None):
         """Sum the screen-space statistic over the ranks, so that every rank takes the same densification decisions; under
         backend "gloo" through the host, as `allreduce_grads`.  Under densify_on="position" there is nothing to sum: every rank
