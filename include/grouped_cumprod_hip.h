@@ -779,6 +779,21 @@ int gcp_mcmc_values(const float* opacity_logit, const float* log_scale, const in
 int gcp_mcmc_noise(float* mean, const float* quat_xyzw, const float* log_scale, const float* opacity_logit, int64_t n_gauss,
                    float amount, float k, float o0, uint32_t seed_lo, uint32_t seed_hi, void* stream);
 
+/* Per-Gaussian contribution to one camera's image (gcp_contrib.hip): with the pair rule of gcp_blend_forward to the letter
+ * — a pixel belongs to a Gaussian if it lies inside the Gaussian's integer box clamped to the frame, g = exp(-0.5 d Λ d^T),
+ * T the exclusive product of 1 - o g over the earlier list entries whose box holds the pixel, w = T o g and w = 0 where
+ * the inclusive product T (1 - o g) is exactly 0 —
+ *   w_max[i] = max_p w,   w_sum[i] = sum_p w   over the pixels p of Gaussian i's box; both 0 for an empty box and for a
+ * Gaussian the binning did not list (a capture-safe capacity that was too small).  Same bins as the blend: tile_off,
+ * tile_start, tile_list of gcp_bin_tiles*, n_tile_pairs = K (or the capacity).  No atomics: every sum is taken in a fixed
+ * order, two calls give the same bits.  n_gauss == 0: nothing is touched; n_tile_pairs == 0: both outputs are zeroed.
+ * No stream synchronise, no read-back.  ws: gcp_blend_contrib_workspace_bytes(K) (8 bytes per entry). */
+size_t gcp_blend_contrib_workspace_bytes(int64_t n_tile_pairs);
+int gcp_blend_contrib(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                      const float* opacity, int64_t n_gauss, int32_t width, int32_t height,
+                      const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start, const int32_t* tile_list,
+                      float* w_max, float* w_sum, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

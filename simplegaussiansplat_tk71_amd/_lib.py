@@ -138,6 +138,9 @@ SIGNATURES = {
     "gcp_mcmc_draw": (ctypes.c_int, [_c_void_p, _i64, _i64, ctypes.c_uint32, ctypes.c_uint32] + [_c_void_p] * 4),
     "gcp_mcmc_values": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i64, ctypes.c_float] + [_c_void_p] * 3),
     "gcp_mcmc_noise": (ctypes.c_int, [_c_void_p] * 4 + [_i64] + [ctypes.c_float] * 3 + [ctypes.c_uint32, ctypes.c_uint32, _c_void_p]),
+    # per-Gaussian contribution from the blend (gcp_contrib.hip): max and sum of the colour weight over each Gaussian's box
+    "gcp_blend_contrib_workspace_bytes": (_sz, [_i64]),
+    "gcp_blend_contrib": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 5 + [_sz, _c_void_p]),
 }
 
 ABI_VERSION = 4

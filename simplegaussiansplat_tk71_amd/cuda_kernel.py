@@ -65,6 +65,7 @@ __all__ = [
     "custom_autograd_grouped_cumprod",
     "RenderDepth",
     "render",
+    "contribution",
     "tile_capacity",
     "capacity_exceeded",
     "GraphedStep",
@@ -688,3 +689,14 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
     for black — the image is then `custom_autograd_grouped_cumprod`'s bit for bit.  The gradient of the background is summed
     over the pixels in a fixed order (the same bits on every run)."""
     return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
+
+
+def contribution(startpoint, endpoint, mean, variance_inverse, opacity, image_width, image_height):
+    """What each of one camera's depth-ordered Gaussians contributes to the image `custom_autograd_grouped_cumprod` / `render`
+    paint from the same arguments -> (w_max f32[N], w_sum f32[N]), detached: the maximum and the sum, over the pixels of the
+    Gaussian's box, of the colour weight w_k = T_k o_k g_k (0 for a dropped pair).  Bins, then `raster.blend_contribution`
+    (csrc/gcp_contrib.hip); no autograd, GPU tensors only.  The maximum is the importance score RadSplat prunes by, the sum
+    LightGaussian's significance; `GS_model_with_param.contribution` folds them over cameras."""
+    with torch.no_grad():
+        bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+        return _raster.blend_contribution(bins, startpoint, endpoint, mean, variance_inverse, opacity)

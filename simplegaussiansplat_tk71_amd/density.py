@@ -1,7 +1,7 @@
 """Density control on the device: the screen-space statistic and the kernel sequence of the one-pass split / clone / prune
-(csrc/gcp_densify.hip), and the MCMC strategy's relocation pass and position noise (csrc/gcp_mcmc.hip).  What belongs to
-the model — parameters, optimiser, statistics — stays in `GS_model_with_param.densify_and_prune_device` and
-`relocate_and_grow_device`."""
+(csrc/gcp_densify.hip), and the MCMC strategy's relocation pass and position noise (csrc/gcp_mcmc.hip), the row gather of a prune by mask (`keep_rows`).
+What belongs to the model — parameters, optimiser, statistics — stays in `GS_model_with_param.densify_and_prune_device`,
+`relocate_and_grow_device` and `prune_rows`."""
 import torch
 
 from . import _lib
@@ -146,3 +146,34 @@ def mcmc_rows(params, moments, n_out, min_opacity, seed):
                    "gcp_mcmc_values")
         new_moments = {k: tuple(rows(t.contiguous(), 1) for t in pair) for k, pair in moments.items()}
     return new, new_moments, {"src_row": src_row, "kind": kind, "times": times, "cum": cum, "weight": weight}
+
+
+def keep_rows(params, moments, keep):
+    """The kernel sequence of `GS_model_with_param.prune_rows`: the kept rows' indices (`keep.nonzero()`, whose size is the one
+    device->host read), then the row gathers of `densify_rows` with that list as the source rows and every row a survivor
+    (kind 0), so parameters and Adam's moments are both carried bit for bit, in order.
+    params, moments: as `densify_rows`; keep: bool (n,) on the parameters' device.  An all-false `keep` raises before anything
+    is gathered.  -> (new params by name, new (exp_avg, exp_avg_sq) by name, m)"""
+    if not all(t.is_cuda for t in params.values()):
+        raise RuntimeError("pruning on the device is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
+    dev, n = params["mean"].device, params["mean"].shape[0]
+    if not (isinstance(keep, torch.Tensor) and keep.dtype == torch.bool and tuple(keep.shape) == (n,) and keep.device == dev):
+        raise RuntimeError(f"keep: expected a bool tensor of shape ({n},) on {dev}")
+    src_row = keep.nonzero().flatten().to(torch.int32)  # the one device->host read: its length
+    m = src_row.numel()
+    if m == 0:
+        raise RuntimeError("keep: no row is kept (an empty scene cannot be rendered or trained)")
+    kind = torch.zeros(m, dtype=torch.uint8, device=dev)  # survivors all
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def rows(t, mode):
+            out = torch.empty((m, *t.shape[1:]), dtype=torch.float32, device=dev)
+            _lib.check(lib.gcp_densify_rows(t.data_ptr(), n, src_row.data_ptr(), kind.data_ptr(), m, t[0].numel(), mode, out.data_ptr(),
+                                            stream), "gcp_densify_rows")
+            return out
+
+        new = {k: rows(t, 0) for k, t in params.items()}
+        new_moments = {k: tuple(rows(t.contiguous(), 1) for t in pair) for k, pair in moments.items()}
+    return new, new_moments, m

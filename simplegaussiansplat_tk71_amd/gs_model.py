@@ -21,6 +21,7 @@ import math
 import torch
 
 from . import density
+from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 from .density import DENSIFY_ON, accumulate_screen_grads
 from .loss import splat_loss
@@ -34,6 +35,7 @@ __all__ = [
     "GS_model_with_param",
     "HipAdam",
     "accumulate_screen_grads",
+    "allreduce_contribution",
     "camera_inputs",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
@@ -74,6 +76,23 @@ def mean_neighbour_distance(n, cloud, batch_size=2000):
         d = torch.cdist(cloud[i:i + batch_size], cloud)
         out[i:i + batch_size] = torch.topk(d, min(n, d.shape[1]), dim=1, largest=False).values.mean(dim=1, keepdim=True)
     return out.repeat(1, 3)
+
+
+def allreduce_contribution(stats, group=None):
+    """The triple of `GS_model_with_param.contribution` over the ranks, in place, when every rank has measured its share of
+    the cameras: w_max by MAX, w_sum and views by SUM, so every rank prunes the same rows.  Under backend "gloo" through the
+    host, as `GS_model_with_param.allreduce_density_stats`.  Returns `stats`."""
+    import torch.distributed as dist
+
+    w_max, w_sum, views = stats
+    for t, op in ((w_max, dist.ReduceOp.MAX), (w_sum, dist.ReduceOp.SUM), (views, dist.ReduceOp.SUM)):
+        if t.is_cuda and dist.get_backend(group) == "gloo":
+            host = t.cpu()
+            dist.all_reduce(host, op=op, group=group)
+            t.copy_(host)
+        else:
+            dist.all_reduce(t, op=op, group=group)
+    return stats
 
 
 class GS_dataset(torch.utils.data.Dataset):
@@ -372,6 +391,72 @@ class GS_model_with_param(torch.nn.Module):
             self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
         self._zero_density_stats(m)
         return n, m
+
+    # ---- prune by what a Gaussian paints (csrc/gcp_contrib.hip) -------------------------------------------------------------
+    @torch.no_grad()
+    def contribution(self, P, K, wh, stats=None):
+        """What every Gaussian contributes to the images of the cameras (P, K, wh) -> (w_max f32[N], w_sum f32[N],
+        views i32[N]): per Gaussian the maximum over all pixels of all cameras, and the sum, of the colour weight
+        w = T o g the blend paints it with (`cuda_kernel.contribution`), and the number of cameras whose list holds it.
+        The cameras are projected with the model's own options (`camera_inputs`), so the opacity measured is the one the
+        blend sees — sigmoid(opacity) rho under antialias=True — with float centres under centres="subpixel".  A camera that
+        sees nothing is skipped; a Gaussian no camera lists keeps 0, 0, 0.
+        `stats`: the triple an earlier call returned; it is accumulated in place and returned, so the training set can be
+        fed in batches.  Cameras are folded in in the order given, one after the other: feeding them one at a time in that
+        order gives the same w_sum bit for bit (w_max and views do in any order).
+        No gradient, no hook, no generator, and the densification statistics are not touched.  GPU only."""
+        cams, _, (width, height) = self.camera_inputs(P, K, wh)
+        n, dev = self.mean.shape[0], self.mean.device
+        if stats is None:
+            stats = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev),
+                     torch.zeros(n, dtype=torch.int32, device=dev))
+        w_max, w_sum, views = stats
+        if not (w_max.shape == w_sum.shape == views.shape == (n,)):
+            raise RuntimeError(f"stats: expected three tensors of shape ({n},), one row per Gaussian")
+        for cam in cams:
+            if cam is None:
+                continue
+            cam_max, cam_sum = _camera_contribution(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
+                                                    width, height)
+            index = cam["index"]  # unique within a camera: plain indexed statements, no atomics
+            w_max[index] = torch.maximum(w_max[index], cam_max)
+            w_sum[index] = w_sum[index] + cam_sum
+            views[index] = views[index] + 1
+        return stats
+
+    @torch.no_grad()
+    def prune_rows(self, keep):
+        """Keep the rows where `keep` (bool [N] on the device) is true, in order, with Adam's state; returns
+        (n_before, n_after).  Parameters and exp_avg / exp_avg_sq are gathered by the row kernel of the device density control
+        (`density.keep_rows`), every tensor's `step` is kept, all statistic arrays come back zeroed at the new length — the
+        bookkeeping of `densify_and_prune_device` after its gather.  One device->host read (the new row count), so it cannot
+        be captured into a graph.  An all-false `keep` raises and leaves the model as it was.  GPU only."""
+        if not self.mean.is_cuda:
+            raise RuntimeError("pruning on the device is a set of HIP kernels: tensors must live on the GPU (no CPU path)")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("prune_rows reads the new row count back: it cannot be captured into a graph")
+        old = {k: getattr(self, k) for k in PARAM_NAMES}
+        n = self.mean.shape[0]
+        states = {k: st for k, st in ((k, self._optimizer.state.get(p)) for k, p in old.items()) if st}
+        new, moments, m = density.keep_rows(
+            {k: p.data.contiguous() for k, p in old.items()}, {k: (st["exp_avg"], st["exp_avg_sq"]) for k, st in states.items()}, keep)
+        for k in PARAM_NAMES:
+            setattr(self, k, torch.nn.Parameter(new[k]))
+        self.changing_optimizer()
+        for k, (exp_avg, exp_avg_sq) in moments.items():
+            self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        self._zero_density_stats(m)
+        return n, m
+
+    def prune_by_contribution(self, stats, threshold=0.01, on="max"):
+        """`prune_rows` on what `contribution` measured: a Gaussian stays if w_max >= threshold (on="max", RadSplat's
+        importance score) or w_sum >= threshold (on="sum", LightGaussian's significance, in pixels); returns
+        (n_before, n_after).  A Gaussian buried behind others, seen by no camera, or too thin to paint `threshold` of any
+        pixel goes, whatever its opacity parameter says.  The default 0.01 is RadSplat's value for the maximum and has NOT been
+        tuned here: no full-length run on real poses exists; for on="sum" choose a threshold of your own."""
+        if on not in ("max", "sum"):
+            raise ValueError(f"on: 'max' or 'sum', got {on!r}")
+        return self.prune_rows(stats[0 if on == "max" else 1] >= threshold)
 
     def allreduce_density_stats(self, group=None):
         """Sum the screen-space statistic over the ranks, so that every rank takes the same densification decisions; under

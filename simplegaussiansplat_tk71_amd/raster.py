@@ -1,6 +1,6 @@
 """Tile binning and fused alpha blending on the HIP library.
 
-Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
+Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
 (include/grouped_cumprod_hip.h).  Everything the reference does around its scan in
 `custom_autograd_grouped_cumprod` (reference: gs_model.py:598-663) happens in three launches here:
 bin (f2), blend forward (f1), blend backward (f1).  No CPU path.
@@ -154,18 +154,23 @@ def bin_tiles(startpoint, endpoint, width, height, capacity=None, counted=None):
     return TileBins(width, height, n, K, tx.value, ty.value, tile_off, tile_start, tile_list[:K])
 
 
-def _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d):
+def _params(startpoint, endpoint, mean, variance_inverse, opacity, l_d=None):
+    """The per-Gaussian arguments of the blend as the C ABI takes them; l_d=None: without colours (`blend_contribution`)."""
     start = _dev_tensor(startpoint, "startpoint", torch.int32, (2,))
     end = _dev_tensor(endpoint, "endpoint", torch.int32, (2,))
     mean_f = _dev_tensor(mean, "mean", torch.float32, (2,))  # reference: mean.to(torch.float32), gs_model.py:679
     vinv = _dev_tensor(variance_inverse, "variance_inverse", torch.float32, (2, 2))
     n = start.size(0)
     op = _dev_tensor(opacity, "opacity", torch.float32).reshape(-1)
-    col = _dev_tensor(l_d, "l_d", torch.float32, (3,))
-    for t, name in ((end, "endpoint"), (mean_f, "mean"), (vinv, "variance_inverse"), (op, "opacity"), (col, "l_d")):
+    out = [start, end, mean_f, vinv, op]
+    names = ["startpoint", "endpoint", "mean", "variance_inverse", "opacity"]
+    if l_d is not None:
+        out.append(_dev_tensor(l_d, "l_d", torch.float32, (3,)))
+        names.append("l_d")
+    for t, name in zip(out[1:], names[1:]):
         _require(t.size(0) == n, f"{name}: {t.size(0)} rows, expected {n}")
         _require(t.device == start.device, f"{name}: on {t.device}, expected {start.device}")
-    return start, end, mean_f, vinv, op, col
+    return tuple(out)
 
 
 def _depth_args(depth, background, n, dev):
@@ -288,6 +293,30 @@ def blend_backward_depth(bins, startpoint, endpoint, mean, variance_inverse, opa
     (summed in a fixed order).  `grad_image` None: zero."""
     return _blend_backward(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward_depth",
                            depth, background, (grad_depth, grad_alpha), background_grad)
+
+
+def blend_contribution(bins, startpoint, endpoint, mean, variance_inverse, opacity):
+    """What every Gaussian contributes to the image `blend_forward` paints on the same bins (gcp_blend_contrib,
+    csrc/gcp_contrib.hip) -> (w_max f32[N], w_sum f32[N]): the maximum and the sum, over the pixels of the Gaussian's box, of
+    the colour weight w = T o g — the pair rule is the forward blend's, a dropped pair (inclusive product exactly 0) has
+    w = 0.  Both are 0 for an empty box, and for a Gaussian that capture-safe bins (`capacity=`) did not list.  No colours, no
+    checkpoints, no atomics: two calls give the same bits."""
+    start, end, mean_f, vinv, op = _params(startpoint, endpoint, mean, variance_inverse, opacity)
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    lib = _lib.load()
+    w_max = torch.empty(n, dtype=torch.float32, device=dev)
+    w_sum = torch.empty(n, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_blend_contrib_workspace_bytes(bins.tile_capacity), dtype=torch.uint8, device=dev)
+        _lib.check(
+            lib.gcp_blend_contrib(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(), n, bins.width,
+                                  bins.height, bins.tile_off.data_ptr(), bins.tile_capacity, bins.tile_start.data_ptr(),
+                                  bins.tile_list.data_ptr(), w_max.data_ptr(), w_sum.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            "gcp_blend_contrib",
+        )
+    return w_max, w_sum
 
 
 def exclusive_scan_i32(x):
