@@ -28,6 +28,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
                                                              # at those iterations drop every Gaussian that paints less than 1 %
                                                              # of any pixel of any training camera (--prune-on sum: less than
                                                              # that many pixels in total), keeping Adam's moments
+    python examples/train_cameras.py --densify mcmc --cap-max 4000 --adam sparse
+                                                             # Adam only on the rows a camera of the batch saw, all five
+                                                             # tensors in one launch (--adam fused: the same launch, every row)
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -90,7 +93,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
-          prune_contribution=None, prune_at=(), prune_on="max"):
+          prune_contribution=None, prune_at=(), prune_on="max", adam="tensor"):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -112,7 +115,13 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `prune_contribution` T with `prune_at` (iterations) and `prune_on` ("max" / "sum"): at those iterations, after the optimiser
     step, every rank measures its share of ALL cameras (`model.contribution`, `batch_size` at a time), the measurements are
     all-reduced, and `model.prune_by_contribution(stats, T, prune_on)` drops the Gaussians below T with Adam's state kept;
-    works with every `densify`."""
+    works with every `densify`.
+    `adam`: the optimiser step (GS_model_with_param): "tensor" (the default), "fused" (one call for all tensors, step counts
+    and rates on the device) or "sparse" (the fused call restricted to the rows some camera of the batch saw on some rank,
+    `grad_iter`; the other rows keep parameters and moments).  Under densify="mcmc" the two regularisers give EVERY row a
+    gradient, and "sparse" does not apply it to the rows no camera saw, as the sparse Adam of other 3DGS trainers."""
+    if adam not in gm.ADAM_MODES:
+        raise ValueError(f"adam: 'tensor', 'fused' or 'sparse', got {adam!r}")
     if densify not in ("reference", "device", "mcmc"):
         raise ValueError(f"densify: 'reference', 'device' or 'mcmc', got {densify!r}")
     if prune_on not in ("max", "sum"):
@@ -128,6 +137,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     opacity = torch.full((n, 1), math.log(opacity_init / (1 - opacity_init)), device=dev)
     sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None, "centres": centres, "cov_dilation": dilation,
           "clamp_colour": clamp_colour}
+    if adam != "tensor":
+        sh["adam"] = adam
     if antialias:
         sh["antialias"] = antialias
     if densify_on != "position":
@@ -174,7 +185,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                 else:
                     torch.distributed.all_reduce(loss)
             model.param_iter_update(grad_iter)
-            model.train_step()
+            model.train_step(visible=grad_iter)
             if densify == "mcmc":
                 model.add_position_noise(seed + iteration, noise_lr)
             iteration += 1
@@ -258,6 +269,10 @@ if __name__ == "__main__":
     ap.add_argument("--prune-at", default="", metavar="I[,I...]", help="iterations at which --prune-contribution runs")
     ap.add_argument("--prune-on", choices=("max", "sum"), default="max",
                     help="max = the largest colour weight T*o*g over every pixel of every camera; sum = their sum")
+    ap.add_argument("--adam", choices=("tensor", "fused", "sparse"), default="tensor",
+                    help="tensor = one Adam kernel per parameter tensor; fused = one call for all of them, step counts and rates on the "
+                         "device; sparse = the fused call on the rows some camera of the batch saw, the others keep parameters and moments "
+                         "(under --densify mcmc the opacity and scale regularisers give every row a gradient: unseen rows are not moved by it)")
     ap.add_argument("--densify-on", choices=("position", "screen"), default="position",
                     help="statistic of --densify device: screen = gradient of the 2-D centres per view (needs --centres subpixel)")
     a = ap.parse_args()
@@ -287,7 +302,7 @@ if __name__ == "__main__":
                       sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply, centres=a.centres,
                       dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on,
                       antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg,
-                      prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on)
+                      prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

@@ -679,6 +679,30 @@ int gcp_ssim_l1_backward(const float* img1, const float* img2, const float* dm_d
 int gcp_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                   double beta2, double eps, int64_t step, void* stream);
 
+/* The same update of up to GCP_ADAM_MAX_TENSORS tensors in ONE call, with step counts and learning rates in device
+ * memory (a captured call replays the step and rate of the replay, not of the capture) and an optional row mask
+ * (the sparse / visibility-masked Adam of other 3DGS trainers).  Two launches on `stream`, no wait, no allocation.
+ *   host arrays of length n_tensors: param, grad, exp_avg, exp_avg_sq (device pointers, 16-byte aligned, contiguous
+ *     float32 [rows[t]][width[t]]), rows (>= 0), width (>= 1), step (device pointers to one int32 each: the number of
+ *     steps already taken).  They are read during the call only.
+ *   lr: DEVICE float[n_tensors].  scal: device float[2 n_tensors], scratch of the caller.
+ *   visible: NULL, or device uint8[rows], non-zero = visible; every tensor of the call must then have the same `rows`.
+ * Prologue kernel, one thread per tensor: step[t] += 1; bc1 = 1 - beta1^step, bc2 = 1 - beta2^step in double;
+ * scal[2t] = (float)(lr[t] / bc1), scal[2t + 1] = (float)(1 / sqrt(bc2)): the two scalars gcp_adam_step forms on the host.
+ * Main kernel: every block belongs to one tensor and grid-strides over that tensor's float4s with gcp_adam_step's arithmetic.
+ * Element e of tensor t lies in row e / width[t].  An element of an invisible row keeps param, exp_avg and exp_avg_sq bit
+ * for bit; a float4 whose four elements all lie in invisible rows is neither loaded nor stored; one that straddles a
+ * visible and an invisible row is loaded whole, updated where visible and stored whole.  step[t] advances whatever the
+ * mask holds, also for a tensor with rows == 0.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: n_tensors outside 0..GCP_ADAM_MAX_TENSORS, a beta outside [0, 1), and with
+ * n_tensors > 0 a NULL host array, lr, scal or step[t], width < 1, rows < 0, rows * width beyond int64, a NULL or
+ * misaligned tensor with elements to process, a mask with unequal rows.  n_tensors == 0 is a no-op. */
+#define GCP_ADAM_MAX_TENSORS 8
+int gcp_adam_step_multi(int32_t n_tensors, float* const* param, const float* const* grad, float* const* exp_avg,
+                        float* const* exp_avg_sq, const int64_t* rows, const int32_t* width, int32_t* const* step,
+                        const float* lr, float* scal, const uint8_t* visible, double beta1, double beta2, double eps,
+                        void* stream);
+
 /* ---- the caller's density control on the device (csrc/gcp_densify.hip) ---------------------
  * Split / clone / prune of gs_model.py:201-265 as one pass whose decisions are all taken from the state BEFORE it, each
  * Gaussian taking one action, and which carries the optimiser's moments of the surviving rows along.  Every entry point

@@ -107,6 +107,8 @@ SIGNATURES = {
     "gcp_project_forward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32, _i32, _i32, ctypes.c_float] + [_c_void_p] * 5),
     "gcp_project_gather": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 11),
     "gcp_adam_step": (ctypes.c_int, [_c_void_p] * 4 + [_i64] + [ctypes.c_double] * 4 + [_i64, _c_void_p]),
+    # n_tensors, host arrays (param, grad, exp_avg, exp_avg_sq, rows, width, step), device lr, scal, visible, betas, eps, stream
+    "gcp_adam_step_multi": (ctypes.c_int, [_i32] + [_c_void_p] * 10 + [ctypes.c_double] * 3 + [_c_void_p]),
     "gcp_ssim_blocks": (_i64, [_i64, _i32, _i32]),
     "gcp_ssim_l1_forward": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float]
                             + [_c_void_p] * 5),

@@ -29,6 +29,7 @@ from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
 PARAM_NAMES = ("mean", "variance_q", "variance_scale", "opacity", "color")  # the per-Gaussian parameters, in optimiser order
+ADAM_MODES = ("tensor", "fused", "sparse")
 
 __all__ = [
     "GS_dataset",
@@ -128,7 +129,7 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
                  active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position",
-                 antialias=False):
+                 antialias=False, adam="tensor"):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
         the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
         clamp_colour, antialias: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
@@ -139,8 +140,17 @@ class GS_model_with_param(torch.nn.Module):
         of the loss's gradient with respect to the 2-D splat centre, per VIEW, scaled by (W/2, H/2) — the NDC unit other
         3DGS trainers threshold in; `forward` and `render` collect it during `backward` in `screen_grads_norm` /
         `screen_grads_views`.  `grad_threshold` has NOT been tuned for that statistic here: no full-length run on real poses
-        exists (the reference's checkout has no images.bin), the default is the reference's value for its own statistic."""
+        exists (the reference's checkout has no images.bin), the default is the reference's value for its own statistic.
+        adam: the optimiser step on the GPU (`HipAdam`).  "tensor" (the default): one kernel per parameter tensor, step counts
+        on the host.  "fused": all five tensors in one call, step counts and rates on the device (capturable).  "sparse": the
+        fused call with the row mask `train_step(visible)` is given — rows outside it keep parameters and moments, as the
+        sparse Adam of other 3DGS trainers; GPU only."""
         super().__init__()
+        if adam not in ADAM_MODES:
+            raise ValueError(f"adam: 'tensor', 'fused' or 'sparse', got {adam!r}")
+        if adam == "sparse" and not mean.is_cuda:
+            raise RuntimeError("adam='sparse' is a HIP kernel: tensors must live on the GPU (CPU models keep torch.optim.Adam)")
+        self.adam = adam
         if densify_on not in DENSIFY_ON:
             raise ValueError(f"densify_on: 'position' or 'screen', got {densify_on!r}")
         if densify_on == "screen" and centres != "subpixel":
@@ -179,7 +189,7 @@ class GS_model_with_param(torch.nn.Module):
         groups = [{"params": p, "lr": float(self.lr[name])} for name, p in self.named_parameters(recurse=False)]
         # on the GPU one streaming kernel per tensor (torch's per-op Adam: 0.95 ms per step at 10^6 Gaussians, its fused
         # multi-tensor form 0.38, HipAdam 0.2)
-        self._optimizer = HipAdam(groups) if self.mean.is_cuda else torch.optim.Adam(groups)
+        self._optimizer = HipAdam(groups, fused=self.adam != "tensor") if self.mean.is_cuda else torch.optim.Adam(groups)
 
     def set_mean_lr(self, iteration):
         """The reference rebuilds Adam (and drops its moments) every step to change one rate (gs_control.py:195-197);
@@ -189,8 +199,15 @@ class GS_model_with_param(torch.nn.Module):
             if name == "mean":
                 group["lr"] = float(self.lr["mean"])
 
-    def train_step(self):
-        self._optimizer.step()
+    def train_step(self, visible=None):
+        """One optimiser step.  `visible` (bool [N] on the device, e.g. `forward`'s grad_iter): the rows adam="sparse" updates,
+        required there; the other modes ignore it."""
+        if self.adam == "sparse":
+            if visible is None:
+                raise RuntimeError("adam='sparse' needs train_step(visible=...): the rows to update (forward's grad_iter)")
+            self._optimizer.step(visible=visible)
+        else:
+            self._optimizer.step()
         self._optimizer.zero_grad(set_to_none=True)
         return self
 
