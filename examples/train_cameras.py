@@ -31,12 +31,16 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --densify mcmc --cap-max 4000 --adam sparse
                                                              # Adam only on the rows a camera of the batch saw, all five
                                                              # tensors in one launch (--adam fused: the same launch, every row)
+    python examples/train_cameras.py --test-every 8 --eval-every 100 --eval-json eval.json
+                                                             # hold out every 8th camera (sorted by name, the llffhold convention),
+                                                             # report PSNR / SSIM / L1 on them every 100 iterations and at the end
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
 perturbed, colour-less copy of them — the same situation as starting from a COLMAP point cloud.
 """
 import argparse
+import json
 import math
 import os
 import sys
@@ -78,14 +82,16 @@ def synthetic_scene(n_gauss, n_cam, width, height, seed, device, with_alpha=Fals
     return (start, P, K, wh, targets, alphas) if with_alpha else (start, P, K, wh, targets)
 
 
-def load_colmap(root, device):
+def load_colmap(root, device, with_names=False):
+    """-> (xyz, P, K, wh, photographs (C, 3, H, W) in 0..1) [+ the image names with_names: what `split_cameras` sorts by]"""
     from PIL import Image
 
     from simplegaussiansplat_tk71_amd import colmap_io
 
     xyz, P, K, wh, names = colmap_io.load_colmap_tensors(os.path.join(root, "sparse", "0"), device=device)
     imgs = [torch.from_numpy(np.array(Image.open(os.path.join(root, "images", n)).convert("RGB"))).permute(2, 0, 1) for n in names]
-    return xyz, P, K, wh, (torch.stack(imgs).float() / 255).to(device)
+    photos = (torch.stack(imgs).float() / 255).to(device)
+    return (xyz, P, K, wh, photos, list(names)) if with_names else (xyz, P, K, wh, photos)
 
 
 def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2, opacity_init=0.1, neighbours=3,
@@ -93,7 +99,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
-          prune_contribution=None, prune_at=(), prune_on="max", adam="tensor"):
+          prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -119,7 +125,17 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `adam`: the optimiser step (GS_model_with_param): "tensor" (the default), "fused" (one call for all tensors, step counts
     and rates on the device) or "sparse" (the fused call restricted to the rows some camera of the batch saw on some rank,
     `grad_iter`; the other rows keep parameters and moments).  Under densify="mcmc" the two regularisers give EVERY row a
-    gradient, and "sparse" does not apply it to the rows no camera saw, as the sparse Adam of other 3DGS trainers."""
+    gradient, and "sparse" does not apply it to the rows no camera saw, as the sparse Adam of other 3DGS trainers.
+    `test_every` N > 0: the cameras are sorted by `names` (default: their index) and every N-th of that order, from the first,
+    is held out (`gs_model.split_cameras`, the llffhold convention): it never enters a batch, the camera extent or a
+    contribution pass, and the run takes exactly the steps of a run that was given the training cameras alone.  Every
+    `eval_every` iterations (0: never) and always after the last step, rank r measures `test[r::world]`
+    (`model.evaluate`: clamped render, per-image PSNR / SSIM / L1 in one HIP pass; over the fixed `background` if there is one,
+    over black under "random" — no colour is drawn for it), `gs_model.gather_metrics` collects the ranks' shares, and rank 0
+    logs the means and appends to the list `evals` a record {"iteration", "split": "test", "views", "gaussians", "psnr",
+    "ssim", "l1", "per_image": {name: {"psnr", "ssim", "l1"}}}, psnr / ssim / l1 being the means of the per-image values.
+    Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
+    network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
         raise ValueError(f"adam: 'tensor', 'fused' or 'sparse', got {adam!r}")
     if densify not in ("reference", "device", "mcmc"):
@@ -129,6 +145,40 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     if isinstance(background, str) and background != "random":
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
+    held = None
+    if test_every:
+        names = [f"{i:06d}" for i in range(P.shape[0])] if names is None else list(names)
+        if len(names) != P.shape[0]:
+            raise ValueError(f"names: {len(names)} entries for {P.shape[0]} cameras")
+        train_idx, test_idx = gm.split_cameras(names, test_every)
+        if not train_idx:
+            raise ValueError(f"test_every={test_every} holds out every camera: nothing is left to train on")
+        keep, out = torch.tensor(train_idx, device=dev), torch.tensor(test_idx, device=dev)
+        held = {"P": P[out], "K": K[out], "wh": wh[out], "targets": targets[out], "names": [str(names[i]) for i in test_idx]}
+        if isinstance(background, tuple) or isinstance(background, list):
+            held["background"] = torch.as_tensor(background, dtype=torch.float32, device=dev)
+            if target_alpha is not None:
+                held["targets"] = held["targets"] + (1 - target_alpha[out]) * held["background"][None, :, None, None]
+        P, K, wh, targets = P[keep], K[keep], wh[keep], targets[keep]
+        target_alpha = None if target_alpha is None else target_alpha[keep]
+
+    def evaluate_held_out():
+        """One record of the held-out cameras; every rank measures its share, rank 0 reports."""
+        n_test = len(held["names"])
+        mine = torch.arange(n_test, device=dev)[rank::world]
+        m = model.evaluate(held["P"][mine], held["K"][mine], held["wh"][mine], held["targets"][mine],
+                           background=held.get("background"), batch_size=batch_size)
+        if world > 1:
+            m = gm.gather_metrics(m, mine, n_test)
+        if rank != 0:
+            return
+        psnr, ssim, l1 = (t.tolist() for t in (m.psnr, m.ssim, m.l1))
+        log(f"iter {iteration:5d}  test PSNR {np.mean(psnr):.3f}  SSIM {np.mean(ssim):.4f}  L1 {np.mean(l1):.5f}  ({n_test} views)")
+        if evals is not None:
+            evals.append({"iteration": iteration, "split": "test", "views": n_test, "gaussians": int(model.mean.shape[0]),
+                          "psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim)), "l1": float(np.mean(l1)),
+                          "per_image": {name: {"psnr": p, "ssim": s, "l1": e} for name, p, s, e in zip(held["names"], psnr, ssim, l1)}})
+
     torch.manual_seed(seed)  # densification draws samples: every rank must draw the same ones
     n = start.shape[0]
     q = torch.zeros((n, 4), device=dev)
@@ -222,8 +272,12 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     model.reset_opacity(reset_opacity_min)
             if iteration % max(1, iterations // 10) == 0 or iteration == iterations:
                 log(f"iter {iteration:5d}  loss {np.mean(losses[-20:]):.5f}  Gaussians {model.mean.shape[0]}")
+            if held is not None and eval_every and iteration % eval_every == 0 and iteration < iterations:
+                evaluate_held_out()
             if iteration >= iterations:
                 break
+    if held is not None:
+        evaluate_held_out()  # always after the last step
     if dev.type == "cuda":
         torch.cuda.synchronize()
     log(f"{iteration} iterations in {time.time() - t0:.1f} s")
@@ -275,7 +329,14 @@ if __name__ == "__main__":
                          "(under --densify mcmc the opacity and scale regularisers give every row a gradient: unseen rows are not moved by it)")
     ap.add_argument("--densify-on", choices=("position", "screen"), default="position",
                     help="statistic of --densify device: screen = gradient of the 2-D centres per view (needs --centres subpixel)")
+    ap.add_argument("--test-every", type=int, default=0, metavar="N",
+                    help="hold out every N-th camera of the name-sorted order, from the first (8: the Mip-NeRF 360 / 3DGS convention; 0: train on all)")
+    ap.add_argument("--eval-every", type=int, default=0, metavar="I",
+                    help="with --test-every: PSNR / SSIM / L1 on the held-out cameras every I iterations (0: only after the last step)")
+    ap.add_argument("--eval-json", default=None, metavar="PATH", help="write the evaluation records (rank 0) as a JSON list")
     a = ap.parse_args()
+    if (a.eval_every or a.eval_json) and not a.test_every:
+        ap.error("--eval-every and --eval-json need --test-every N with N > 0")
     if a.antialias and not (a.dilation is not None and a.dilation > 0):
         ap.error("--antialias requires --dilation F with F > 0")
     prune_at = tuple(int(v) for v in a.prune_at.split(",") if v)
@@ -290,9 +351,9 @@ if __name__ == "__main__":
             torch.distributed.init_process_group("nccl", device_id=device)
         else:
             torch.distributed.init_process_group(a.backend)
-    alphas = None
+    alphas, names, evals = None, None, []
     if a.colmap:
-        start, P, K, wh, targets = load_colmap(a.colmap, device)
+        start, P, K, wh, targets, names = load_colmap(a.colmap, device, with_names=True)
     elif background is not None:
         start, P, K, wh, targets, alphas = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device, with_alpha=True)
     else:
@@ -302,7 +363,11 @@ if __name__ == "__main__":
                       sh_frame=a.sh_frame, sh_every=a.sh_every, save_ply=a.save_ply, load_ply=a.load_ply, centres=a.centres,
                       dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on,
                       antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg,
-                      prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam)
+                      prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam,
+                      test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names)
+    if a.eval_json and rank == 0:
+        with open(a.eval_json, "w") as f:
+            json.dump(evals, f, indent=1)
     if rank == 0:
         print(f"loss {np.mean(losses[:10]):.5f} -> {np.mean(losses[-10:]):.5f}")
     if world > 1:

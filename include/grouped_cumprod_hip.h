@@ -670,6 +670,22 @@ int gcp_ssim_l1_backward(const float* img1, const float* img2, const float* dm_d
                          int64_t planes, int32_t height, int32_t width, const float* window11_host, const float* scales,
                          float* grad_img1, void* stream);
 
+/* ---- held-out evaluation: per-image squared error, L1 and SSIM in one pass ------------------------------------------
+ * img, ref: float[images][channels][height][width].  For every image, out[3 i ..] = (mean (a - b)^2, mean |a - b|, mean
+ * SSIM(a, b)) over its channels * height * width elements, in double; SSIM as in gcp_ssim_l1_forward (11-tap window in
+ * HOST memory, reflect padding, c1, c2).  flags: a set of GCP_METRICS_* bits; with GCP_METRICS_CLAMP img (only img: ref is
+ * the photograph) is clamped to [0, 1] as it is read, so all three terms see the clamped value.  PSNR is
+ * 10 log10(L^2 / out[3 i]) and is left to the caller.
+ * Two kernels on `stream`, no device->host read, no allocation (capturable): one block per 32 x 16 tile writes its three
+ * float sums to partial (float[3 * gcp_ssim_blocks(images * channels, height, width)], written before it is read); one
+ * block per image adds that image's partials in double in a fixed order.  No atomics: the same bits on every run, and an
+ * image's numbers do not depend on what else is in the batch.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: images < 0, channels <= 0, height or width < 6, a NULL window, an unknown
+ * flag bit; with images > 0 a NULL array or more than 2^31 - 1 blocks.  images == 0 is a no-op after the scalar checks. */
+#define GCP_METRICS_CLAMP 1
+int gcp_image_metrics(const float* img, const float* ref, int64_t images, int32_t channels, int32_t height, int32_t width,
+                      const float* window11_host, float c1, float c2, int32_t flags, float* partial, double* out, void* stream);
+
 /* ---- the caller's optimiser step ---------------------------------------------------------
  * torch.optim.Adam's update (no weight decay, no amsgrad; gs_model.py:43-47, :64-67) of one parameter tensor of n
  * floats, in place: exp_avg = beta1 exp_avg + (1 - beta1) grad; exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) grad^2;

@@ -113,6 +113,9 @@ SIGNATURES = {
     "gcp_ssim_l1_forward": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float]
                             + [_c_void_p] * 5),
     "gcp_ssim_l1_backward": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    # img, ref, images, channels, height, width, host window, c1, c2, GCP_METRICS_* flags, partial, out (double), stream
+    "gcp_image_metrics": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float, _i32]
+                          + [_c_void_p] * 3),
     "gcp_project_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 10),
     "gcp_project_gather_depth": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
     "gcp_project_backward_depth": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 11),
@@ -147,6 +150,7 @@ SIGNATURES = {
 
 ABI_VERSION = 4
 SPLAT_CLAMP_COLOUR, SPLAT_ANTIALIAS = 1, 2  # GCP_SPLAT_* of the header
+METRICS_CLAMP = 1  # GCP_METRICS_CLAMP
 
 _lib = None
 

@@ -37,6 +37,19 @@ __device__ __forceinline__ float block_sum(float v, float* s_red) {
   return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
+// Three block sums behind one barrier, each with the association of block_sum; s_red: float[3][4].
+__device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float (*s_red)[4]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64), b += __shfl_down(b, off, 64), c += __shfl_down(c, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) s_red[0][threadIdx.x >> 6] = a, s_red[1][threadIdx.x >> 6] = b, s_red[2][threadIdx.x >> 6] = c;
+  __syncthreads();
+  a = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);
+  b = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]);
+  c = (s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3]);
+}
+
 __global__ __launch_bounds__(kThreads) void k_ssim_l1_fwd(const float* __restrict__ img1, const float* __restrict__ img2,
                                                          int height, int width, int tiles_x, int tiles_y, Window win, float c1,
                                                          float c2, float* __restrict__ dm_dmu1, float* __restrict__ dm_de11,
@@ -167,6 +180,103 @@ __global__ __launch_bounds__(kThreads) void k_ssim_l1_bwd(const float* __restric
   }
 }
 
+// Evaluation (no gradient, no maps): the tiling, staging and blurs of k_ssim_l1_fwd, with three sums per block — the SSIM
+// map, |a - b| and (a - b)^2 — at partial[3 * block ..].  clamp: img1 (the render; never the photograph) is clamped to
+// [0, 1] as it is staged, so that all three terms see the clamped value (NaN stays NaN).  8 B read per pixel-channel.
+__global__ __launch_bounds__(kThreads) void k_image_metrics(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                           int height, int width, int tiles_x, int tiles_y, Window win, float c1,
+                                                           float c2, int clamp, float* __restrict__ partial) {
+  __shared__ float s_a[kHH][kHW + 1], s_b[kHH][kHW + 1];
+  __shared__ float s_h[5][kHH][kTW + 1];
+  __shared__ float s_red[3][4];
+  const int tile = blockIdx.x % (tiles_x * tiles_y), plane = blockIdx.x / (tiles_x * tiles_y);
+  const int x0 = (tile % tiles_x) * kTW, y0 = (tile / tiles_x) * kTH;
+  const float* a = img1 + (i64)plane * height * width;
+  const float* b = img2 + (i64)plane * height * width;
+  const float lo = clamp ? 0.f : -__builtin_inff(), hi = clamp ? 1.f : __builtin_inff();
+  for (int i = threadIdx.x; i < kHH * kHW; i += kThreads) {
+    const int r = i / kHW, c = i % kHW;
+    // rows / columns past the image edge of a partial tile are clamped: their results are never used
+    const int y = reflect(min(y0 + r - kR, height - 1 + kR), height), x = reflect(min(x0 + c - kR, width - 1 + kR), width);
+    // both loads first, then two selects against uniform bounds (+-inf without the clamp: the identity): a branch on the
+    // loaded value would hold the second load back until the first has returned
+    const float va = a[(i64)y * width + x], vb = b[(i64)y * width + x];
+    s_a[r][c] = va < lo ? lo : (va > hi ? hi : va);
+    s_b[r][c] = vb;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHH * kTW; i += kThreads) {  // blur along the row
+    const int r = i / kTW, c = i % kTW;
+    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float va = s_a[r][c + k], vb = s_b[r][c + k], w = win.w[k];
+      m1 += w * va, m2 += w * vb, e11 += w * (va * va), e22 += w * (vb * vb), e12 += w * (va * vb);
+    }
+    s_h[0][r][c] = m1, s_h[1][r][c] = m2, s_h[2][r][c] = e11, s_h[3][r][c] = e22, s_h[4][r][c] = e12;
+  }
+  __syncthreads();
+  float sum_ssim = 0.f, sum_l1 = 0.f, sum_sq = 0.f;
+  const int c = threadIdx.x % kTW;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {  // blur along the column, two pixels per thread
+    const int r = threadIdx.x / kTW + half * (kTH / 2);
+    const int x = x0 + c, y = y0 + r;
+    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float w = win.w[k];
+      mu1 += w * s_h[0][r + k][c], mu2 += w * s_h[1][r + k][c], e11 += w * s_h[2][r + k][c], e22 += w * s_h[3][r + k][c],
+          e12 += w * s_h[4][r + k][c];
+    }
+    if (x < width && y < height) {
+      const float s1 = e11 - mu1 * mu1, s2 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
+      const float A = 2.f * mu1 * mu2 + c1, B = 2.f * s12 + c2, C = mu1 * mu1 + mu2 * mu2 + c1, D = s1 + s2 + c2;
+      const float d = s_a[r + kR][c + kR] - s_b[r + kR][c + kR];
+      sum_ssim += A * B / (C * D + 1e-12f);
+      sum_l1 += fabsf(d);
+      sum_sq += d * d;
+    }
+  }
+  block_sum3(sum_ssim, sum_l1, sum_sq, s_red);
+  if (threadIdx.x == 0) {
+    float* p = partial + 3 * (i64)blockIdx.x;
+    p[0] = sum_ssim, p[1] = sum_l1, p[2] = sum_sq;
+  }
+}
+
+// One block per image: its channels x tiles partials of k_image_metrics lie next to each other (block = plane * tiles +
+// tile, plane = image * channels + c).  Added in double in a fixed order — strided per thread, then a fixed LDS tree, no
+// atomics — and divided by the image's element count: out[image] = (mean (a-b)^2, mean |a-b|, mean SSIM).
+__global__ __launch_bounds__(kThreads) void k_metrics_fold(const float* __restrict__ partial, i64 per_image, double count,
+                                                          double* __restrict__ out) {
+  __shared__ double s_acc[3][kThreads];
+  const float* p = partial + 3 * per_image * (i64)blockIdx.x;
+  double ssim = 0.0, l1 = 0.0, sq = 0.0;
+  i64 i = threadIdx.x;
+  for (; i + 7 * kThreads < per_image; i += 8 * kThreads) {  // eight loads in flight; added in the order of the plain loop
+    float v[8][3];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float* q = p + 3 * (i + u * kThreads);
+      v[u][0] = q[0], v[u][1] = q[1], v[u][2] = q[2];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) ssim += (double)v[u][0], l1 += (double)v[u][1], sq += (double)v[u][2];
+  }
+  for (; i < per_image; i += kThreads) ssim += (double)p[3 * i], l1 += (double)p[3 * i + 1], sq += (double)p[3 * i + 2];
+  s_acc[0][threadIdx.x] = sq, s_acc[1][threadIdx.x] = l1, s_acc[2][threadIdx.x] = ssim;
+  __syncthreads();
+  for (int off = kThreads / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s_acc[k][threadIdx.x] += s_acc[k][threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) out[3 * (i64)blockIdx.x + threadIdx.x] = s_acc[threadIdx.x][0] / count;
+}
+
 bool make_window(const float* window11_host, Window& w) {
   if (!window11_host) return false;
   for (int k = 0; k < kTaps; ++k) w.w[k] = window11_host[k];
@@ -209,6 +319,25 @@ int gcp_ssim_l1_backward(const float* img1, const float* img2, const float* dm_d
   const int tx = (width + kTW - 1) / kTW, ty = (height + kTH - 1) / kTH;
   hipLaunchKernelGGL(k_ssim_l1_bwd, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, img1, img2, dm_dmu1, dm_de11,
                      dm_de12, (int)height, (int)width, tx, ty, win, scales, grad_img1);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+int gcp_image_metrics(const float* img, const float* ref, int64_t images, int32_t channels, int32_t height, int32_t width,
+                      const float* window11_host, float c1, float c2, int32_t flags, float* partial, double* out, void* stream) {
+  Window win;
+  if (images < 0 || channels <= 0 || height < kR + 1 || width < kR + 1 || (flags & ~GCP_METRICS_CLAMP) || !make_window(window11_host, win))
+    return GCP_ERR_INVALID_ARGUMENT;
+  if (images == 0) return GCP_OK;
+  if (images > 0x7fffffff / channels) return GCP_ERR_INVALID_ARGUMENT;  // the plane count alone is past one grid
+  const int64_t blocks = gcp_ssim_blocks(images * channels, height, width);
+  if (blocks > 0x7fffffff || !img || !ref || !partial || !out) return GCP_ERR_INVALID_ARGUMENT;
+  const int tx = (width + kTW - 1) / kTW, ty = (height + kTH - 1) / kTH;
+  hipLaunchKernelGGL(k_image_metrics, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, img, ref, (int)height, (int)width,
+                     tx, ty, win, c1, c2, (int)(flags & GCP_METRICS_CLAMP), partial);
+  GCP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_metrics_fold, dim3((unsigned)images), dim3(kThreads), 0, (hipStream_t)stream, (const float*)partial,
+                     (i64)channels * tx * ty, (double)channels * (double)height * (double)width, out);
   GCP_HIP(hipGetLastError());
   return GCP_OK;
 }

@@ -66,6 +66,7 @@ __all__ = [
     "RenderDepth",
     "render",
     "contribution",
+    "paint",
     "tile_capacity",
     "capacity_exceeded",
     "GraphedStep",
@@ -700,3 +701,18 @@ def contribution(startpoint, endpoint, mean, variance_inverse, opacity, image_wi
     with torch.no_grad():
         bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
         return _raster.blend_contribution(bins, startpoint, endpoint, mean, variance_inverse, opacity)
+
+
+def paint(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth=None, background=None):
+    """The image `custom_autograd_grouped_cumprod` (depth None) or `render` (depth [N] given; `background` float[3] on the
+    device or None) paints from the same arguments -> (H+1, W+1, 3), detached, for evaluation: bins, then `raster.blend_forward`
+    / `raster.blend_forward_depth` WITHOUT transmittance checkpoints — nothing is kept for a backward, there is no autograd
+    node.  Under `tile_capacity` the bins are the capture-safe ones, as in the Functions.  GPU tensors only."""
+    with torch.no_grad():
+        bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+        if depth is None:
+            if background is not None:
+                raise RuntimeError("paint: a background is composited by the depth blend: pass the Gaussians' depths")
+            return _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False)
+        return _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
+                                           with_checkpoints=False)[0]

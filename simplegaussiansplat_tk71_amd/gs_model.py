@@ -23,8 +23,9 @@ import torch
 from . import density
 from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
+from .cuda_kernel import paint as _paint
 from .density import DENSIFY_ON, accumulate_screen_grads
-from .loss import splat_loss
+from .loss import ImageMetrics, image_metrics, psnr_from_mse, splat_loss
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
@@ -35,13 +36,17 @@ __all__ = [
     "GS_dataset",
     "GS_model_with_param",
     "HipAdam",
+    "ImageMetrics",
     "accumulate_screen_grads",
     "allreduce_contribution",
     "camera_inputs",
+    "gather_metrics",
+    "image_metrics",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
     "mean_neighbour_distance",
     "splat_loss",
+    "split_cameras",
 ]
 
 
@@ -94,6 +99,41 @@ def allreduce_contribution(stats, group=None):
         else:
             dist.all_reduce(t, op=op, group=group)
     return stats
+
+
+def split_cameras(names, test_every=8):
+    """(train_idx, test_idx): index lists into `names`.  The cameras are sorted by name and position i of that order is held
+    out for testing where i % test_every == 0 — the `llffhold` convention of Mip-NeRF 360 and 3DGS, so the numbers compare
+    with published ones.  Both lists are in sorted-name order.  test_every=0: everything trains, nothing is held out."""
+    test_every = int(test_every)
+    if test_every < 0:
+        raise ValueError(f"test_every: >= 0, got {test_every}")
+    order = sorted(range(len(names)), key=lambda i: names[i])
+    if test_every == 0:
+        return order, []
+    return [j for i, j in enumerate(order) if i % test_every], [j for i, j in enumerate(order) if i % test_every == 0]
+
+
+def gather_metrics(metrics, index, total, group=None):
+    """Every rank has measured its share of `total` images (`metrics`: the ImageMetrics of the images `index`, a list or
+    int64 tensor of positions in 0..total-1; both may be empty) -> the ImageMetrics of all of them on every rank: the share is
+    scattered into zero vectors of length `total` and these are all-reduced with SUM — under backend "gloo" through the host,
+    as `allreduce_contribution`.  Every image is measured by exactly one rank, so a sum adds zeros to its value: the result
+    is the single-rank one bit for bit.  `psnr` is recomputed from the summed `mse` (max_val 1)."""
+    import torch.distributed as dist
+
+    dev = metrics.mse.device
+    index = torch.as_tensor(index, dtype=torch.int64, device=dev)
+    full = torch.zeros(3, int(total), dtype=torch.float64, device=dev)
+    if index.numel():
+        full[:, index] = torch.stack((metrics.mse, metrics.l1, metrics.ssim)).to(torch.float64)
+    if full.is_cuda and dist.get_backend(group) == "gloo":
+        host = full.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        full.copy_(host)
+    else:
+        dist.all_reduce(full, op=dist.ReduceOp.SUM, group=group)
+    return ImageMetrics(full[0], full[1], full[2], psnr_from_mse(full[0]))
 
 
 class GS_dataset(torch.utils.data.Dataset):
@@ -594,3 +634,40 @@ class GS_model_with_param(torch.nn.Module):
         depth = depth[:, None, 1:, 1:].contiguous()
         alpha = alpha[:, None, 1:, 1:].contiguous()
         return [images, depth, alpha, names, grad_iter]
+
+    @torch.no_grad()
+    def evaluate(self, P, K, wh, targets, background=None, batch_size=4, clamp=True):
+        """Image quality on the cameras (P, K, wh) against `targets` (C, 3, H, W) -> `ImageMetrics` (mse, l1, ssim, psnr:
+        float64 (C,) on the device), one entry per camera, in order.  The cameras are projected with the model's own options
+        and painted as `render` paints them (`background`: float[3] on the device or None for black; the [1:, 1:] crop,
+        (B, 3, H, W)) by `cuda_kernel.paint` — the blend without transmittance checkpoints, no autograd node — `batch_size`
+        at a time, each batch measured in one pass (`image_metrics`; `clamp`: the render is clamped to [0, 1] first).
+        A camera that sees no Gaussian is NOT dropped: its image is the background (or black) and it is measured like the
+        others.  Nothing of the training state is touched: no `.grad`, no densification statistic, no optimiser state, no
+        generator — a training run with evaluations in it takes the same steps as one without.  The metrics stay on the
+        device; the host reads are those of the projection and the binning.  GPU only.  LPIPS is not computed."""
+        n_cam = P.shape[0]
+        if targets.dim() != 4 or targets.shape[0] != n_cam:
+            raise RuntimeError(f"targets: expected (C, 3, H, W) with one image per camera ({n_cam})")
+        batch_size = max(1, int(batch_size))
+        with_depth = background is not None
+        parts = []
+        for c in range(0, n_cam, batch_size):
+            cams, _, (width, height) = self.camera_inputs(P[c:c + batch_size], K[c:c + batch_size], wh[c:c + batch_size],
+                                                          with_depth=with_depth)
+            frames = []
+            for cam in cams:
+                if cam is None:  # nothing in view: the background alone
+                    frame = torch.zeros(height + 1, width + 1, 3, dtype=torch.float32, device=self.mean.device)
+                    if with_depth:
+                        frame += background.detach().to(frame).reshape(1, 1, 3)
+                else:
+                    frame = _paint(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
+                                   width, height, cam["depth"] if with_depth else None, background)
+                frames.append(frame)
+            images = torch.stack(frames, dim=0)[:, 1:, 1:, :].permute(0, 3, 1, 2)
+            parts.append(image_metrics(images, targets[c:c + batch_size], clamp=clamp))
+        if not parts:
+            empty = torch.zeros(0, dtype=torch.float64, device=self.mean.device)
+            return ImageMetrics(empty, empty.clone(), empty.clone(), empty.clone())
+        return ImageMetrics(*(torch.cat(field) for field in zip(*parts)))

@@ -1,5 +1,8 @@
 """The training loss on the HIP library: (1 - lambda) L1 + lambda (1 - mean SSIM), one kernel per direction
-(csrc/gcp_loss.hip).  The PyTorch formulation it is tested against: oracle/loss_torch.py."""
+(csrc/gcp_loss.hip), and the evaluation metrics on the same tiling: per-image squared error, L1 and SSIM in one pass
+(`image_metrics`).  The PyTorch formulation both are tested against: oracle/loss_torch.py."""
+from typing import NamedTuple
+
 import torch
 
 from . import _lib
@@ -66,3 +69,43 @@ def splat_loss(images, targets, lamda=0.2):
     gs_control.py:180-182, kornia.metrics.ssim).  Both terms and their gradient are one HIP kernel per direction
     (csrc/gcp_loss.hip); GPU tensors only.  The PyTorch formulation it is tested against: oracle/loss_torch.py."""
     return _SplatLoss.apply(images, targets, float(lamda), 1.0)
+
+
+class ImageMetrics(NamedTuple):
+    """One entry per image, float64 on the device: mean squared error, mean |a - b|, mean SSIM, and
+    psnr = 10 log10(max_val^2 / mse) (inf where mse == 0)."""
+    mse: torch.Tensor
+    l1: torch.Tensor
+    ssim: torch.Tensor
+    psnr: torch.Tensor
+
+
+def psnr_from_mse(mse, max_val=1.0):
+    """10 log10(max_val^2 / mse) with torch, on mse's device; inf where mse == 0."""
+    return 10.0 * torch.log10((max_val * max_val) / mse)
+
+
+def image_metrics(images, targets, clamp=True, max_val=1.0):
+    """Per-image evaluation metrics of (B, C, H, W) `images` against `targets` -> ImageMetrics of float64 (B,) device tensors.
+    One HIP pass over both (gcp_image_metrics, csrc/gcp_loss.hip): SSIM with the 11-tap Gaussian window and reflect padding of
+    `splat_loss`, c1, c2 = (0.01 max_val)^2, (0.03 max_val)^2.  clamp=True: `images` (never `targets`) is clamped to [0, 1] as
+    it is read — what an 8-bit file of the render would hold, and what other 3DGS trainers evaluate — and all three terms see
+    the clamped value.  An image's numbers depend on that image alone, and two calls give the same bits (no atomics).  No
+    autograd (the outputs are detached), no device->host read; the inputs need not be contiguous or float32 (converted as
+    `splat_loss` converts them).  GPU tensors only.  LPIPS is not computed: it needs pretrained network weights."""
+    if not images.is_cuda:
+        raise RuntimeError("image_metrics is a HIP kernel: tensors must live on the GPU (no CPU path)")
+    if images.shape != targets.shape or images.dim() != 4:
+        raise RuntimeError("image_metrics expects two (B, C, H, W) tensors of one shape")
+    a, b = images.detach().contiguous().float(), targets.detach().contiguous().float()
+    bsz, ch, h, w = a.shape
+    lib = _lib.load()
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        partial = torch.empty(lib.gcp_ssim_blocks(bsz * ch, h, w), 3, dtype=torch.float32, device=a.device)
+        out = torch.empty(bsz, 3, dtype=torch.float64, device=a.device)
+        _lib.check(lib.gcp_image_metrics(a.data_ptr(), b.data_ptr(), bsz, ch, h, w, _host_window(11, 1.5), (0.01 * max_val) ** 2,
+                                         (0.03 * max_val) ** 2, _lib.METRICS_CLAMP if clamp else 0, partial.data_ptr(),
+                                         out.data_ptr(), stream), "gcp_image_metrics")
+    mse, l1, ssim = out.t().contiguous().unbind(dim=0)
+    return ImageMetrics(mse, l1, ssim, psnr_from_mse(mse, max_val))
