@@ -99,7 +99,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           reset_opacity_min=0.01, seed=0, log=print, rank=0, world=1, background=None, target_alpha=None, sh_degree=2,
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
-          prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None):
+          prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
+          screen_grad="signed"):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -118,6 +119,11 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `relocate_and_grow_device(seed + iteration, cap_max)` relocates the dead Gaussians and grows the scene by 5 % up to
     `cap_max` (None: no growth); no opacity reset and no statistic: every rank draws the same samples from the same
     parameters).  `densify_on`: the statistic the device path decides on, "position" or "screen" (GS_model_with_param).
+    `screen_grad`: what the "screen" statistic takes the norm of, "signed" (the default) or "abs" — the per-pixel absolute
+    gradients of the centre summed per component (AbsGS; gsplat's absgrad), which does not cancel over a large splat; the
+    optimiser steps are those of "signed" bit for bit.  The densification threshold (the model's `grad_threshold`) is not
+    tuned for this statistic here either: no full-length run on real poses exists.  As a pointer, not a default: trainers
+    that switch to absolute gradients raise theirs by a factor of about four (gsplat: 2e-4 -> 8e-4).
     `prune_contribution` T with `prune_at` (iterations) and `prune_on` ("max" / "sum"): at those iterations, after the optimiser
     step, every rank measures its share of ALL cameras (`model.contribution`, `batch_size` at a time), the measurements are
     all-reduced, and `model.prune_by_contribution(stats, T, prune_on)` drops the Gaussians below T with Adam's state kept;
@@ -193,6 +199,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         sh["antialias"] = antialias
     if densify_on != "position":
         sh["densify_on"] = densify_on
+    if screen_grad != "signed":
+        sh["screen_grad"] = screen_grad
     if load_ply is not None:
         model = gm.GS_model_with_param.from_ply(load_ply, dev, **sh)
     else:
@@ -329,6 +337,9 @@ if __name__ == "__main__":
                          "(under --densify mcmc the opacity and scale regularisers give every row a gradient: unseen rows are not moved by it)")
     ap.add_argument("--densify-on", choices=("position", "screen"), default="position",
                     help="statistic of --densify device: screen = gradient of the 2-D centres per view (needs --centres subpixel)")
+    ap.add_argument("--screen-grad", choices=("signed", "abs"), default="signed",
+                    help="with --densify-on screen: abs = per-pixel absolute gradients of the centre summed per component (AbsGS), "
+                         "which do not cancel over a large splat; the threshold is not tuned for it")
     ap.add_argument("--test-every", type=int, default=0, metavar="N",
                     help="hold out every N-th camera of the name-sorted order, from the first (8: the Mip-NeRF 360 / 3DGS convention; 0: train on all)")
     ap.add_argument("--eval-every", type=int, default=0, metavar="I",
@@ -364,7 +375,8 @@ if __name__ == "__main__":
                       dilation=a.dilation, clamp_colour=a.clamp_colour, densify=a.densify, densify_on=a.densify_on,
                       antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg,
                       prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam,
-                      test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names)
+                      test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names,
+                      screen_grad=a.screen_grad)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

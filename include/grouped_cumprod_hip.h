@@ -834,6 +834,29 @@ int gcp_blend_contrib(const int32_t* start_xy, const int32_t* end_xy, const floa
                       const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start, const int32_t* tile_list,
                       float* w_max, float* w_sum, void* ws, size_t ws_bytes, void* stream);
 
+/* Absolute screen-space gradient of one camera (gcp_absgrad.hip; AbsGS, gsplat's absgrad).  For every splat-pixel pair
+ * (k, p) that gcp_blend_backward counts, with its T_k, g_k, c_k = <grad_image(p), l_k> (+ grad_depth_map(p) z_k) and suffix
+ * recursion R_k (R = 0 behind the list; depth call: <grad_image, background> - grad_alpha_map where T_N != 0):
+ *   m(k,p) = T_k o_k g_k (c_k - R_k) Λ_k (p - mean_k),   Λ (p - mean) = (A dx + C dy, B dx + D dy), vinv = [[A, B], [C, D]]
+ * and m = 0 outside the box clamped to the frame and for a dropped pair.  grad_mean[k] of the backward is sum_p m(k,p);
+ *   absgrad[k] = ( sum_p |m_x(k,p)|, sum_p |m_y(k,p)| ),  float [N,2]
+ * — 0 for an empty box and for a Gaussian the binning did not list.  The arguments are the backward's inputs (the same
+ * bins, `t_ckpt` of the matching forward); grad_depth_map, grad_alpha_map and background may be NULL (zero / black), every
+ * other pointer is required.  No atomics: two calls give the same bits.  n_gauss == 0: nothing is touched;
+ * n_tile_pairs == 0: absgrad is zeroed.  No stream synchronise, no read-back, no allocation.
+ * ws: gcp_blend_absgrad_workspace_bytes(K) (8 bytes per entry). */
+size_t gcp_blend_absgrad_workspace_bytes(int64_t n_tile_pairs);
+int gcp_blend_absgrad(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                      const float* opacity, const float* l_d, int64_t n_gauss, int32_t width, int32_t height,
+                      const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start, const int32_t* tile_list,
+                      const float* t_ckpt, const float* grad_image, float* absgrad, void* ws, size_t ws_bytes, void* stream);
+int gcp_blend_absgrad_depth(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                            const float* opacity, const float* l_d, const float* depth, const float* background,
+                            int64_t n_gauss, int32_t width, int32_t height, const int32_t* tile_off, int64_t n_tile_pairs,
+                            const int32_t* tile_start, const int32_t* tile_list, const float* t_ckpt, const float* grad_image,
+                            const float* grad_depth_map, const float* grad_alpha_map, float* absgrad, void* ws,
+                            size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,10 @@ SIGNATURES = {
     # per-Gaussian contribution from the blend (gcp_contrib.hip): max and sum of the colour weight over each Gaussian's box
     "gcp_blend_contrib_workspace_bytes": (_sz, [_i64]),
     "gcp_blend_contrib": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 5 + [_sz, _c_void_p]),
+    # absolute screen-space gradient (gcp_absgrad.hip): the backward's inputs, then absgrad [N,2], ws, ws_bytes, stream
+    "gcp_blend_absgrad_workspace_bytes": (_sz, [_i64]),
+    "gcp_blend_absgrad": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 6 + [_sz, _c_void_p]),
+    "gcp_blend_absgrad_depth": (ctypes.c_int, [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 8 + [_sz, _c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -66,6 +66,7 @@ __all__ = [
     "RenderDepth",
     "render",
     "contribution",
+    "absgrad_buffer",
     "paint",
     "tile_capacity",
     "capacity_exceeded",
@@ -583,6 +584,30 @@ def _saved_with_bins(ctx):
     return tensors, _raster.TileBins(*ctx.bins_meta, tile_off, tile_start, tile_list)
 
 
+def absgrad_buffer(startpoint):
+    """A float32 [N, 2] tensor of zeros on the device of `startpoint` ([N, 2]): what `custom_autograd_grouped_cumprod`,
+    `RenderDepth` and `render` take as `absgrad`.  For a captured step (`GraphedStep`) allocate it before the capture and
+    read it after every replay: the captured backward writes to that address."""
+    return torch.zeros(startpoint.shape[0], 2, dtype=torch.float32, device=startpoint.device)
+
+
+def _absgrad_argument(ctx, extra, startpoint):
+    """The optional trailing `absgrad` of the two Functions: at most one argument, None or a buffer the backward can write.
+    The node remembers how many inputs it was given (its backward returns as many gradients)."""
+    if len(extra) > 1:
+        raise TypeError(f"expected at most one trailing argument (absgrad), got {len(extra)}")
+    ctx.n_absgrad = len(extra)
+    buf = extra[0] if extra else None
+    if buf is None:
+        return None
+    n = startpoint.shape[0]
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.float32 and tuple(buf.shape) == (n, 2)
+            and buf.is_contiguous() and not buf.requires_grad and buf.device == startpoint.device):
+        raise RuntimeError(f"absgrad: expected a contiguous float32 [{n}, 2] tensor on {startpoint.device} that does not require grad "
+                           "(cuda_kernel.absgrad_buffer), or None")
+    return buf
+
+
 class custom_autograd_grouped_cumprod(torch.autograd.Function):
     """The reference's rasterise-and-blend Function, same name and call signature
     (reference: gs_model.py:477-820; call site gs_model.py:449):
@@ -594,6 +619,11 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
     splat-pixel pairs, sorting, scanning, un-sorting and scatter-adding (gs_model.py:598-624), the
     Gaussians are binned into 16x16 tiles and blended per pixel in one fused kernel
     (csrc/gcp_blend.hip); backward returns the same four gradients (gs_model.py:820).
+
+    One optional trailing argument, `absgrad` (default None): a float32 [N, 2] device tensor (`absgrad_buffer`), not
+    differentiable, which `backward` fills — right after the ordinary backward, with a kernel on the same stream — with the
+    absolute screen-space gradient of that call's grad_image (`raster.blend_absgrad`, csrc/gcp_absgrad.hip).  The four
+    gradients are the same bits with and without it; without it no further kernel is launched.
 
     Differences, all documented in DESIGN.md:
       * `boxsize` and `batch` are accepted and ignored: they exist to chunk the pair list for
@@ -623,8 +653,9 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, boxsize, batch, startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width,
-                image_height):
+                image_height, *absgrad):
         _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d)
+        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
         with torch.no_grad():
             bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
             image, t_ckpt = _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d,
@@ -642,18 +673,24 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
             g_mean, g_vinv, g_op, g_l = _raster.blend_backward(
                 bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, pixel_sum_grad
             )
+            if ctx.absgrad is not None:
+                _raster.blend_absgrad(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, pixel_sum_grad,
+                                      out=ctx.absgrad)
         g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
-        return None, None, None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, None, None
+        return (None, None, None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, None, None) + (None,) * ctx.n_absgrad
 
 
 class RenderDepth(torch.autograd.Function):
     """The Function's blend with an expected-depth map, an alpha map and a background colour (csrc/gcp_blend.hip,
     k_blend_fwd_depth / k_blend_bwd_depth); see `render`.  Capture-safe and overflow-reporting under `tile_capacity` /
-    `GraphedStep` as `custom_autograd_grouped_cumprod`."""
+    `GraphedStep` as `custom_autograd_grouped_cumprod`, and with the same optional trailing `absgrad` buffer, filled by
+    `raster.blend_absgrad_depth` for the gradients of all three maps."""
 
     @staticmethod
-    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background):
+    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                *absgrad):
         _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
+        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
         ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
         with torch.no_grad():
             bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
@@ -670,12 +707,15 @@ class RenderDepth(torch.autograd.Function):
             g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
                 bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
                 background, background_grad=want_bg)
+            if ctx.absgrad is not None:
+                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
+                                            g_depth, g_alpha, background, out=ctx.absgrad)
         g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
         return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
-                g_bg.reshape(background.shape) if want_bg else None)
+                g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
 
 
-def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None):
+def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None):
     """Rasterise and blend one camera's depth-ordered Gaussians (the arguments of `custom_autograd_grouped_cumprod`, without
     boxsize / batch) -> (image (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), differentiable in mean (if float),
     variance_inverse, opacity, l_d, depth and background.
@@ -688,8 +728,14 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
       image(p) = sum_k w_k l_k + T_N(p) * background.
     `background`: a float[3] tensor on the device (no host read: a captured step may change it between replays), or None
     for black — the image is then `custom_autograd_grouped_cumprod`'s bit for bit.  The gradient of the background is summed
-    over the pixels in a fixed order (the same bits on every run)."""
-    return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
+    over the pixels in a fixed order (the same bits on every run).
+    `absgrad`: None, or a float32 [N, 2] device tensor (`absgrad_buffer`) that `backward` fills with the absolute screen-space
+    gradient of the three maps' gradients (`raster.blend_absgrad_depth`); not differentiable, and the gradients of the other
+    arguments are the same bits with and without it."""
+    if absgrad is None:
+        return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
+    return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                             absgrad)
 
 
 def contribution(startpoint, endpoint, mean, variance_inverse, opacity, image_width, image_height):

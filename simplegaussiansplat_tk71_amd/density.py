@@ -7,6 +7,9 @@ import torch
 from . import _lib
 
 DENSIFY_ON = ("position", "screen")
+# what densify_on="screen" accumulates per view: the norm of the centre's gradient as the blend backward returns it — a signed
+# sum over the splat's pixels — or of the per-pixel absolute values summed per component (AbsGS; csrc/gcp_absgrad.hip)
+SCREEN_GRADS = ("signed", "abs")
 
 
 def accumulate_screen_grads(grad_xy, index, scale, norm_acc, view_count, validate=False):

@@ -21,10 +21,11 @@ import math
 import torch
 
 from . import density
+from .cuda_kernel import absgrad_buffer as _absgrad_buffer
 from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 from .cuda_kernel import paint as _paint
-from .density import DENSIFY_ON, accumulate_screen_grads
+from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
 from .loss import ImageMetrics, image_metrics, psnr_from_mse, splat_loss
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
@@ -169,7 +170,7 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
                  active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position",
-                 antialias=False, adam="tensor"):
+                 antialias=False, adam="tensor", screen_grad="signed"):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
         the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
         clamp_colour, antialias: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
@@ -181,6 +182,13 @@ class GS_model_with_param(torch.nn.Module):
         3DGS trainers threshold in; `forward` and `render` collect it during `backward` in `screen_grads_norm` /
         `screen_grads_views`.  `grad_threshold` has NOT been tuned for that statistic here: no full-length run on real poses
         exists (the reference's checkout has no images.bin), the default is the reference's value for its own statistic.
+        screen_grad: what densify_on="screen" takes the norm of.  "signed" (the default): the centre's gradient as the blend
+        backward returns it, a signed sum over the splat's pixels — a large, blurry Gaussian that is too bright on one side and
+        too dark on the other cancels there and is never split.  "abs" (needs densify_on="screen"): the per-pixel absolute
+        values summed per component (AbsGS; gsplat's absgrad=True; csrc/gcp_absgrad.hip), collected in one [m, 2] buffer per
+        drawn camera; the parameters' gradients, and so the optimiser steps, are bit for bit those of "signed".
+        `grad_threshold` is not tuned for this statistic here either; it is larger than the signed one by construction, and
+        trainers that switch raise their threshold with it (gsplat: 2e-4 -> 8e-4) — a pointer, not a default.
         adam: the optimiser step on the GPU (`HipAdam`).  "tensor" (the default): one kernel per parameter tensor, step counts
         on the host.  "fused": all five tensors in one call, step counts and rates on the device (capturable).  "sparse": the
         fused call with the row mask `train_step(visible)` is given — rows outside it keep parameters and moments, as the
@@ -193,6 +201,10 @@ class GS_model_with_param(torch.nn.Module):
         self.adam = adam
         if densify_on not in DENSIFY_ON:
             raise ValueError(f"densify_on: 'position' or 'screen', got {densify_on!r}")
+        if screen_grad not in SCREEN_GRADS:
+            raise ValueError(f"screen_grad: 'signed' or 'abs', got {screen_grad!r}")
+        if screen_grad == "abs" and densify_on != "screen":
+            raise ValueError("screen_grad='abs' is a form of the screen-space statistic: it needs densify_on='screen' (and so centres='subpixel')")
         if densify_on == "screen" and centres != "subpixel":
             raise ValueError("densify_on='screen' needs centres='subpixel': with pixel centres the blend has no gradient w.r.t. the centre")
         if not 0 <= L_max <= 3:
@@ -220,7 +232,7 @@ class GS_model_with_param(torch.nn.Module):
         self._L_max, self.sh_frame, self.active_sh_degree = L_max, sh_frame, active_sh_degree
         self.centres, self.cov_dilation, self.clamp_colour, self.antialias = centres, cov_dilation, clamp_colour, antialias
         self.reference_layout = reference_layout
-        self.densify_on = densify_on
+        self.densify_on, self.screen_grad = densify_on, screen_grad
         self._zero_density_stats(mean.shape[0])
         self.changing_optimizer()
 
@@ -533,7 +545,10 @@ class GS_model_with_param(torch.nn.Module):
 
     def _watch_centres(self, cams, width, height):
         """densify_on="screen": hooks on the cameras' float centres that add the norm of their gradient, scaled to NDC units
-        (W/2, H/2), to `screen_grads_norm` and one view to `screen_grads_views` when `backward` reaches them."""
+        (W/2, H/2), to `screen_grads_norm` and one view to `screen_grads_views` when `backward` reaches them.
+        screen_grad="abs": every such camera also gets its "absgrad" buffer ([m, 2], handed to the Function by `forward` /
+        `render`), and the hook accumulates that buffer instead of the signed gradient — the Function's backward has filled it
+        by the time the gradient of its input reaches the hook."""
         if self.densify_on != "screen" or not torch.is_grad_enabled():
             return
         if torch.cuda.is_current_stream_capturing():
@@ -542,7 +557,11 @@ class GS_model_with_param(torch.nn.Module):
         scale = (0.5 * width, 0.5 * height)
         for cam in cams:
             if cam is not None and cam["mean"].requires_grad:
-                cam["mean"].register_hook(lambda grad, index=cam["index"]: self._accumulate_centres(grad, index, scale))
+                if self.screen_grad == "abs":
+                    cam["absgrad"] = _absgrad_buffer(cam["startpoint"])
+                    cam["mean"].register_hook(lambda grad, index=cam["index"], buf=cam["absgrad"]: self._accumulate_centres(buf, index, scale))
+                else:
+                    cam["mean"].register_hook(lambda grad, index=cam["index"]: self._accumulate_centres(grad, index, scale))
 
     def _accumulate_centres(self, grad, index, scale):
         if self.screen_grads_norm.numel() != self.mean.shape[0]:
@@ -607,9 +626,10 @@ class GS_model_with_param(torch.nn.Module):
 
         def draw(cam):
             batch = cam["boxsize"].new_tensor([cam["boxsize"].numel()])
+            extra = (cam["absgrad"],) if cam.get("absgrad") is not None else ()  # screen_grad="abs" (`_watch_centres`)
             return (custom_autograd_grouped_cumprod.apply(
                 cam["boxsize"], batch, cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"],
-                cam["opacity"], cam["l_d"], width, height),)
+                cam["opacity"], cam["l_d"], width, height, *extra),)
 
         (out,), names = self._draw_cameras(cams, image_sample, draw)
         out = out[:, 1:, 1:, :]
@@ -629,7 +649,7 @@ class GS_model_with_param(torch.nn.Module):
         (images, depth, alpha), names = self._draw_cameras(
             cams, range(P.shape[0]) if image_sample is None else image_sample,
             lambda cam: render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
-                               cam["depth"], width, height, background))
+                               cam["depth"], width, height, background, cam.get("absgrad")))
         images = images[:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
         depth = depth[:, None, 1:, 1:].contiguous()
         alpha = alpha[:, None, 1:, 1:].contiguous()

@@ -1,6 +1,6 @@
 """Tile binning and fused alpha blending on the HIP library.
 
-Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
+Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_absgrad.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
 (include/grouped_cumprod_hip.h).  Everything the reference does around its scan in
 `custom_autograd_grouped_cumprod` (reference: gs_model.py:598-663) happens in three launches here:
 bin (f2), blend forward (f1), blend backward (f1).  No CPU path.
@@ -317,6 +317,69 @@ def blend_contribution(bins, startpoint, endpoint, mean, variance_inverse, opaci
             "gcp_blend_contrib",
         )
     return w_max, w_sum
+
+
+def _blend_absgrad(bins, params, t_ckpt, grad_image, forward_name, depth=None, background=None, grad_maps=None, out=None):
+    """Both absolute-gradient entry points; grad_maps None: colour only, else (grad_depth, grad_alpha) of the depth call.
+    out: a contiguous float32 [N, 2] tensor on the device to write instead of a new one."""
+    with_depth = grad_maps is not None
+    start, end, mean_f, vinv, op, col = _params(*params)
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    shape = (bins.height + 1, bins.width + 1)
+    if with_depth:
+        z, bg = _depth_args(depth, background, n, dev)
+        if grad_image is None:
+            grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
+    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
+    _require(tuple(gimg.shape) == shape + (3,), f"grad_image: expected shape {shape + (3,)}")
+    maps = []
+    for t, name in zip(grad_maps or (), ("grad_depth", "grad_alpha")):
+        if t is not None:
+            t = _dev_tensor(t, name, torch.float32)
+            _require(tuple(t.shape) == shape, f"{name}: expected shape {shape}")
+        maps.append(t)
+    lib = _lib.load()
+    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
+    _require(ck.numel() >= _checkpoint_floats(lib, bins),
+             f"t_ckpt: too small for these bins (pass what {forward_name}(..., with_checkpoints=True) returned)")
+    if out is None:
+        absgrad = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    else:
+        absgrad = out
+        _require(isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.float32
+                 and tuple(out.shape) == (n, 2) and out.is_contiguous() and not out.requires_grad,
+                 f"absgrad: expected a contiguous float32 [{n}, 2] tensor on {dev} that does not require grad")
+    name = "gcp_blend_absgrad_depth" if with_depth else "gcp_blend_absgrad"
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_blend_absgrad_workspace_bytes(bins.tile_capacity), dtype=torch.uint8, device=dev)
+        _lib.check(
+            getattr(lib, name)(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(), col.data_ptr(),
+                               *((z.data_ptr(), _ptr(bg)) if with_depth else ()), n, bins.width, bins.height,
+                               bins.tile_off.data_ptr(), bins.tile_capacity, bins.tile_start.data_ptr(), bins.tile_list.data_ptr(),
+                               ck.data_ptr(), gimg.data_ptr(), *(_ptr(t) for t in maps), absgrad.data_ptr(),
+                               ws.data_ptr(), ws.numel(), _stream(dev)),
+            name,
+        )
+    return absgrad
+
+
+def blend_absgrad(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, t_ckpt, grad_image, out=None):
+    """The absolute screen-space gradient (gcp_blend_absgrad, csrc/gcp_absgrad.hip; AbsGS, gsplat's absgrad) from the arguments
+    of `blend_backward` -> f32 [N, 2]: per Gaussian (sum_p |m_x|, sum_p |m_y|) over the splat-pixel pairs the backward counts,
+    m(k, p) being the pair's term of `blend_backward`'s grad_mean — which is sum_p m(k, p), a signed sum in which the two
+    sides of a large splat cancel.  0 for an empty box, and for a Gaussian that capture-safe bins (`capacity=`) did not list.
+    No atomics: two calls give the same bits.  out: a float32 [N, 2] device tensor to fill instead of a new one."""
+    return _blend_absgrad(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward", out=out)
+
+
+def blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, grad_image,
+                        grad_depth=None, grad_alpha=None, background=None, out=None):
+    """`blend_absgrad` for the loss of `blend_backward_depth`: <image, grad_image> + <depth_map, grad_depth> + <alpha,
+    grad_alpha> (None: zero), the image composited over `background` (None: black) -> f32 [N, 2]."""
+    return _blend_absgrad(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward_depth",
+                          depth, background, (grad_depth, grad_alpha), out=out)
 
 
 def exclusive_scan_i32(x):
