@@ -23,32 +23,22 @@
 //       few slots.  (An entry-parallel variant with the pair values parked in LDS was measured
 //       slower, 1.88 vs 1.69 ms: it cannot skip the waves an entry does not touch.)
 //       No float atomics anywhere => bitwise reproducible.
+//   The staging of a list chunk, the back-to-front walk itself (T_k, c_k - R_k, the recurrence; the slow and the dead chunk), the
+//   slot address and the per-Gaussian slot reduction live in gcp_blend_shared.hpp, where gcp_absgrad.hip and gcp_contrib.hip
+//   take them from too; this file holds the forward walk, what the backward does per entry, the folds and the host side.
 
 #include <hip/hip_runtime.h>
-#include <type_traits>
 #include <stdint.h>
 
-#include "gcp_tiles.hpp"
+#include "gcp_blend_shared.hpp"
 
 namespace {
 using namespace gcp;
 
-constexpr int kStageBwd = 32;       // (backward; LDS also holds the per-pixel-row partial sums)
-constexpr int kCkpt = kStageBwd;    // the forward saves every pixel's transmittance every kCkpt list entries
-static_assert(kStage % kCkpt == 0 && 64 % kCkpt == 0 && kCkpt <= 32, "checkpoints fall on hit-word boundaries");
 constexpr int kGradVals = 9;        // per (tile, Gaussian) slot: go, gl0..2, S(c dx), S(c dy), S(c dx dx), S(c dx dy), S(c dy dy)
 constexpr int kGradValsDepth = 10;  // (depth variant: + S(dL/dD w), the depth gradient)
 constexpr int kRowVals = 7;         // per pixel row in LDS: go, gl0..2, S(c), S(c dx), S(c dx dx)   (dy is constant along a row)
 constexpr int kRowSlots = 8;        // LDS slots per pixel row (the transposed reduction below leaves 8 values in 8 lane classes)
-
-// sum over each 16-lane DPP row (= one pixel row of the tile); valid in lanes 15, 31, 47, 63
-__device__ __forceinline__ float row_sum16(float v) {
-  v += dpp_f<0x111, 0xf>(0.0f, v);
-  v += dpp_f<0x112, 0xf>(0.0f, v);
-  v += dpp_f<0x114, 0xf>(0.0f, v);
-  v += dpp_f<0x118, 0xf>(0.0f, v);
-  return v;
-}
 
 // One step of the transposed reduction: lanes with `second` false keep value a, the others keep b; each adds its
 // partner's copy of the value it keeps (partner = DPP pattern CTRL, which must flip the class bit).
@@ -58,72 +48,7 @@ __device__ __forceinline__ float xchg_sum(bool second, float a, float b) {
   return keep + dpp_f<CTRL, 0xf>(0.0f, send);
 }
 
-// The depth / alpha / background variant of the blend (gcp_blend_forward_depth / gcp_blend_backward_depth).  Per pixel,
-// with w_k = T_k o_k g_k as for the colour and T_N the transmittance behind the whole list:
-//   depth = sum_k w_k z_k (not divided by alpha),   alpha = 1 - T_N,   image += T_N bg.
-// In the backward the background and the alpha map are one more, fully absorbing layer behind the list: the recursion
-// starts at R_N = dL/dI . bg - dL/dA (0 where T_N == 0: an exact zero, or an underflow whose true derivative is
-// negligible) and c_k gains dL/dD z_k.
-struct DepthArgs {
-  const float* z;           // [N] camera-space depth of every Gaussian
-  const float* bg;          // float[3] background colour, or nullptr (black)
-  float* depth;             // forward: [(H+1)(W+1)] expected depth
-  float* alpha;             // forward: [(H+1)(W+1)] 1 - T_N
-  const float* grad_depth;  // backward: dL/d(depth map), or nullptr (zero)
-  const float* grad_alpha;  // backward: dL/d(alpha map), or nullptr (zero)
-  float* tile_bg;           // backward: [n_tiles][3] per-tile sums of dL/dI T_N, or nullptr (no background gradient)
-};
-
-template <int STAGE>
-struct Staged {
-  int4 box[STAGE];     // x0, y0, x1-x0, y1-y0 (clamped to the image)
-  float4 geo[STAGE];   // mx, my, opacity, box mask as bits (0-15: tile columns inside the box, 16-31: tile rows)
-  float4 vin[STAGE];   // Λ' = -0.5*log2(e) * Λ, Λ = [[a,b],[c,d]]: a b c d (forward) or a, b + c, d, - (backward)
-  float4 col[STAGE];   // l0 l1 l2, 1/opacity (0 if opacity == 0; read by no kernel) — the depth variant stages z there
-  // hits[w][c]: bit j set = staged entry 64*c + j reaches into the four pixel rows of wave w.  A wave walks the set
-  // bits of its own words (scalar s_ff1 / s_andn2) and never sees the entries that miss it.
-  unsigned long long hits[4][(STAGE + 63) / 64];
-};
-
-template <int STAGE, bool QUAD3, bool DEPTH = false>
-__device__ __forceinline__ void stage_entries(const BlendArgs& a, Staged<STAGE>& s, int first, int cnt, int tile_x0, int tile_y0,
-                                              const float* z = nullptr) {
-  for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
-    const i64 g = a.tile_list[first + j];
-    Box b;
-    load_box(a.start, a.end, g, a.W, a.H, b);
-    s.box[j] = make_int4(b.x0, b.y0, b.x1 - b.x0, b.y1 - b.y0);
-    // the box as two 16-bit masks over the tile's columns and rows: membership of a pixel is ONE and + ONE compare
-    // against the lane's own two bits
-    const int c0 = max(b.x0 - tile_x0, 0), c1 = min(b.x1 - tile_x0, kTile - 1);
-    const int r0 = max(b.y0 - tile_y0, 0), r1 = min(b.y1 - tile_y0, kTile - 1);
-    const unsigned cm = (c1 >= c0) ? ((2u << c1) - (1u << c0)) : 0u;
-    const unsigned rm = (r1 >= r0) ? ((2u << r1) - (1u << r0)) : 0u;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {  // entries j of one 64-lane staging wave form one word per target wave
-      const unsigned long long touched = __ballot(((rm >> (4 * w2)) & 0xfu) != 0u);
-      if ((threadIdx.x & 63) == 0) s.hits[w2][j >> 6] = touched;
-    }
-    const float op = a.opacity[g];
-    s.geo[j] = make_float4(a.mean[2 * g], a.mean[2 * g + 1], op, __uint_as_float(cm | (rm << 16)));
-    // Λ pre-scaled by -0.5*log2(e): g = exp(-0.5 d Λ d^T) becomes ONE v_exp_f32 of d Λ' d^T.  The extra rounding of
-    // Λ' moves g by < 1e-7 absolute (relative 6e-8*|log2 g|, and g decays as fast as that factor grows).
-    constexpr float kS = -0.5f * 1.44269504088896341f;
-    // QUAD3 (backward): a, b + c, d — the quadratic form in five VALU instead of six; the forward keeps a, b, c, d and the
-    // association of the reference's two matmuls: its per-entry chain is latency-bound and the shorter form is 6 % slower there
-    s.vin[j] = QUAD3 ? make_float4(kS * a.vinv[4 * g], kS * a.vinv[4 * g + 1] + kS * a.vinv[4 * g + 2], kS * a.vinv[4 * g + 3], 0.0f)
-                     : make_float4(kS * a.vinv[4 * g], kS * a.vinv[4 * g + 1], kS * a.vinv[4 * g + 2], kS * a.vinv[4 * g + 3]);
-    s.col[j] = make_float4(a.l_d[3 * g], a.l_d[3 * g + 1], a.l_d[3 * g + 2], DEPTH ? z[g] : (op != 0.0f ? 1.0f / op : 0.0f));
-  }
-}
-
-// Transmittance checkpoints: slot q of tile t holds every pixel's transmittance in front of list entry first + q kCkpt,
-// for q = 0 .. ceil(n / kCkpt) — the last one is the transmittance behind the whole list — 256 floats each (one per
-// pixel of the tile, thread order).  Tile t's slots start at first / kCkpt + 2 t: consecutive tiles never overlap
-// (floor(first/c) + ceil(n/c) + 1 <= floor((first+n)/c) + 2), so K / kCkpt + 2 n_tiles + 2 slots hold them all without a
-// separate prefix sum.
-__device__ __forceinline__ i64 ckpt_slot0(int first, int tile) { return (i64)(first / kCkpt) + 2 * (i64)tile; }
-inline size_t ckpt_floats(i64 n_tile_pairs, int n_tiles) {
+inline size_t ckpt_floats(i64 n_tile_pairs, int n_tiles) {  // the checkpoint slots of gcp_blend_shared.hpp: ckpt_slot0
   return (size_t)((n_tile_pairs > 0 ? n_tile_pairs : 0) / kCkpt + 2 * (i64)n_tiles + 2) * 256u;
 }
 
@@ -133,7 +58,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendArgs& a, float* __rest
   // The blend kernels are VALU-issue bound: let a*b+c contract into v_fma_f32 here (the library is otherwise built
   // with -ffp-contract=off).  One rounding instead of two per contraction; results stay within the 1e-5 bar.
 #pragma clang fp contract(fast)
-  __shared__ Staged<kStage> s;
+  __shared__ StagedCol<kStage> s;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave id in an SGPR: the row test below is scalar
   const int tile = blockIdx.x;
@@ -147,7 +72,7 @@ __device__ __forceinline__ void blend_fwd_tile(const BlendArgs& a, float* __rest
   for (int base = first; base < last; base += kStage) {
     const int cnt = __builtin_amdgcn_readfirstlane(min(kStage, last - base));  // scalar loop bound
     __syncthreads();
-    stage_entries<kStage, false, DEPTH>(a, s, base, cnt, (tile % a.tiles_x) * kTile, (tile / a.tiles_x) * kTile, da.z);
+    stage_entries<false, DEPTH>(a, s, base, cnt, (tile % a.tiles_x) * kTile, (tile / a.tiles_x) * kTile, da.z);
     __syncthreads();
     // Only the entries whose rows reach this wave (hits[w]), in list order.  Every listed entry is used, so all
     // three of its LDS records are read together, ahead of the membership branch.  (Reading one entry ahead of the
@@ -221,34 +146,6 @@ __global__ __launch_bounds__(256) void k_blend_fwd_depth(const BlendArgs a, cons
   blend_fwd_tile<CKPT, true>(a, image, t_ckpt, da);
 }
 
-// Backward: per (tile, entry) partial sums, written to the entry's Gaussian-major slot.
-//
-// Per pixel, with k running over the list entries whose box holds the pixel, T_k the exclusive transmittance,
-// a_k = o_k g_k, c_k = (dL/dI . l_k), p_k = T_k a_k l_k (gs_model.py:500):
-//   S_k = sum_{j>k} (dL/dI . p_j)                    exclusive suffix sum, gs_model.py:716-722
-//   S_k / (1 - a_k) = T_k R_k,   R_{k-1} = a_k c_k + (1 - a_k) R_k = R_k + a_k (c_k - R_k),   R_last = 0
-//   dL/do_k    = T_k g_k (c_k - R_k)                 gs_model.py:733-740   (= gp/o - (g/anti) S)
-//   "common"_k = T_k a_k (c_k - R_k)                 gs_model.py:747-748, :757-758   (= gp - (a/anti) S)
-//   dL/dl_k    = dL/dI T_k a_k                       (true gradient; the reference's is channel-collapsed, Q2)
-// The list is walked back to front, one staged chunk of kStageBwd entries at a time, in ONE pass: the transmittance in
-// front of an entry comes from the one behind it, T_k = T_{k+1} / (1 - a_k) (v_rcp_f32, 1 ulp), restarted at every chunk
-// from the checkpoint the forward kernel saved for the chunk's END — so the quotients never chain further than one chunk
-// (<= 32 roundings, ~2e-6 relative) and nothing is subtracted or accumulated in T.  A quotient cannot undo an
-// underflow: a chunk in which some pixel's transmittance falls below FLT_MIN (at most one chunk per pixel) is handled by
-// its wave with T_k recomputed front to back from the chunk's START checkpoint for every entry instead (exact; the product
-// up to an entry's group of eight is formed once per group: ~160 entry evaluations per chunk, two more registers).  g_k = 0 where the pixel is outside the box or the pair was dropped
-// (gs_model.py:560) — such an entry then contributes exactly nothing.  Every gradient term is T_k times a convex
-// combination of the c_j: its round-off is relative to the layer's own transmittance at any depth.
-// T behind staged entry j for this lane's pixel, given T in front of it: T * (1 - o_j g_j) inside the entry's box, T outside
-template <int STAGE>
-__device__ __forceinline__ float slow_factor(const Staged<STAGE>& s, int j, float fx, float fy, unsigned lane_bits, float T) {
-  const float4 gj = s.geo[j];
-  const float4 vj = s.vin[j];
-  const float dxj = fx - gj.x, dyj = fy - gj.y;
-  const float g_j = __builtin_amdgcn_exp2f(dxj * (vj.x * dxj + vj.y * dyj) + (vj.z * dyj) * dyj);
-  return ((__float_as_uint(gj.w) & lane_bits) == lane_bits) ? T * (1.0f - gj.z * g_j) : T;
-}
-
 // the sums of three per-pixel values over the tile in a fixed order (a butterfly per wave, then the four waves in order),
 // written by threads 0-2: no atomics, the same bits on every run
 __device__ __forceinline__ void tile_sum3(float v0, float v1, float v2, float* out) {
@@ -263,6 +160,9 @@ __device__ __forceinline__ void tile_sum3(float v0, float v1, float v2, float* o
   if (threadIdx.x < 3) out[threadIdx.x] = ((s_w[0][threadIdx.x] + s_w[1][threadIdx.x]) + s_w[2][threadIdx.x]) + s_w[3][threadIdx.x];
 }
 
+// Backward: per (tile, entry) partial sums, written to the entry's Gaussian-major slot.  The walk (T_k, c_k, R_k; the quotient,
+// the slow chunk, the dead chunk) is walk_back of gcp_blend_shared.hpp; here is what the backward does per entry — seven or
+// eight per-lane values summed along each pixel row of the tile — and the fold of the rows into the slot.
 template <bool DEPTH>
 __device__ __forceinline__ void blend_bwd_tile(const BlendArgs& a, const int* __restrict__ tile_off,
                                                const float* __restrict__ t_ckpt,
@@ -271,114 +171,26 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendArgs& a, const int* __
                                                const DepthArgs& da) {
 #pragma clang fp contract(fast)  // as in k_blend_fwd
   constexpr int kVals = DEPTH ? kGradValsDepth : kGradVals;
-  __shared__ Staged<kStageBwd> s;
+  __shared__ StagedCol<kStageBwd> s;
   // [entry][pixel row of the tile * kRowSlots + value]; one word of padding per entry: the fold below reads with one
   // thread per entry, and a stride of 128 words would put all of them on one LDS bank
   constexpr int kPartStride = 16 * kRowSlots + 1;
   __shared__ float s_part[kStageBwd][kPartStride];
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave id in an SGPR: the row test below is scalar
-  const int tile = blockIdx.x;
-  const int ttx = tile % a.tiles_x, tty = tile / a.tiles_x;
-  const int px = ttx * kTile + (lane & 15);
-  const int py = tty * kTile + w * 4 + (lane >> 4);
-  const float fx = (float)px, fy = (float)py;
-  const int first = a.tile_start[tile], last = a.tile_start[tile + 1];
-  float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
-  if (px <= a.W && py <= a.H) {
-    const i64 o = ((i64)py * (a.W + 1) + px) * 3;
-    g0 = grad_image[o]; g1 = grad_image[o + 1]; g2 = grad_image[o + 2];
-  }
-  const unsigned lane_bits = (1u << (lane & 15)) | (1u << (16 + w * 4 + (lane >> 4)));
+  const WalkPixel p = walk_pixel<DEPTH>(a, t_ckpt, grad_image, da);
+  const int lane = p.lane;
+  const float g0 = p.g0, g1 = p.g1, g2 = p.g2, gz = p.gz;
   const bool b1 = lane & 2;
-  float* const row_slot = &s_part[0][(w * 4 + (lane >> 4)) * kRowSlots + ((lane & 2) ? 4 : 0) + ((lane & 4) ? 2 : 0) + ((lane & 8) ? 1 : 0)];
-  const float* const ck = t_ckpt + ckpt_slot0(first, tile) * 256 + threadIdx.x;
-  static_assert(kStageBwd <= 32, "one 32-bit word of hits per wave");
-  const int nchunks = (last - first + kStageBwd - 1) / kStageBwd;
-  float R = 0.0f;  // R_k of the deepest entry handled so far (the suffix behind the end of the list is empty)
-  float gz = 0.0f;  // dL/dD of this pixel (depth variant)
-  if (DEPTH) {
-    const float T_N = ck[(i64)nchunks * 256];
-    float ga = 0.0f;
-    if (px <= a.W && py <= a.H) {
-      const i64 p = (i64)py * (a.W + 1) + px;
-      if (da.grad_depth) gz = da.grad_depth[p];
-      if (da.grad_alpha) ga = da.grad_alpha[p];
-    }
-    const float cb = da.bg ? g0 * da.bg[0] + g1 * da.bg[1] + g2 * da.bg[2] : 0.0f;
-    R = (T_N != 0.0f) ? cb - ga : 0.0f;  // the absorbing layer behind the list (DepthArgs)
-    if (da.tile_bg) tile_sum3(g0 * T_N, g1 * T_N, g2 * T_N, da.tile_bg + 3 * (i64)tile);
-  }
-  for (int q = nchunks - 1; q >= 0; --q) {
-    const int base = first + q * kStageBwd;
-    const int cnt = __builtin_amdgcn_readfirstlane(min(kStageBwd, last - base));  // scalar loop bound
-    // transmittance behind this chunk (the next chunk's start, or the end of the list) and in front of it; issued ahead
-    // of the staging: their latency hides behind the barrier
-    const float T_end = ck[(i64)(q + 1) * 256];
-    const float T_start = (q > 0) ? ck[(i64)q * 256] : 1.0f;
-    __syncthreads();
-    stage_entries<kStageBwd, true, DEPTH>(a, s, base, cnt, ttx * kTile, tty * kTile, da.z);
-    __syncthreads();
-    // only the entries whose rows reach this wave, deepest first (the fold below skips this wave's rows for the others,
-    // so nothing needs zeroing)
-    const unsigned hits = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)s.hits[w][0]);
-    // wave-uniform: some pixel of the strip underflows inside this chunk — quotients cannot be trusted for it
-    const bool slow = __ballot(T_end < 1.17549435e-38f && T_start != 0.0f) != 0ull;
-    float Tn = T_end;  // transmittance behind the entry in hand
-    float T_group = T_start;
-    int slow_group = -1;
-    auto walk_chunk = [&](auto slow_tag) {
-    constexpr bool kSlow = decltype(slow_tag)::value;
-    unsigned h = hits;
-    while (h) {
-      const int k = 31 - __builtin_clz(h);
-      h &= ~(1u << k);
-      {
-        // straight-line for all 64 lanes; lanes outside the box / dropped pairs are zeroed with selects
-        const float4 ge = s.geo[k];
-        const float4 vi = s.vin[k];
-        const float4 co = s.col[k];
-        const bool in = (__float_as_uint(ge.w) & lane_bits) == lane_bits;
-        const float dx = fx - ge.x, dy = fy - ge.y;
-        // (d Λ) d^T (gs_model.py:495) as a dx^2 + (b + c) dx dy + d dy^2
-        const float gv = __builtin_amdgcn_exp2f(dx * (vi.x * dx + vi.y * dy) + (vi.z * dy) * dy);
-        const float og = ge.z * gv;
-        const float anti = 1.0f - og;                       // gs_model.py:535
-        float Tk, incl;
-        if (!kSlow) {
-          incl = Tn;                                          // what the forward pass left behind this pair
-          Tk = (Tn == 0.0f) ? 0.0f : Tn * __builtin_amdgcn_rcpf(anti);
-        } else {
-          // T_k front to back from the chunk's start checkpoint: the same products in the same order for every entry, but not
-          // from scratch for each — the product up to the entry's group of eight slots is formed once per group (the walk
-          // visits the groups back to front: 0 + 8 + 16 + 24 slots) and only the group's own earlier slots per entry
-          // (<= 7): about 160 entry evaluations per chunk instead of 496.  A scene whose pixels underflow at different
-          // depths takes this branch in many chunks of a wave (blend backward 0.81 -> 2.0 ms with the Gaussians crowding the
-          // image centre, before this).
-          const unsigned below_group = (1u << (k & ~7)) - 1u;
-          if ((k & ~7) != slow_group) {  // wave-uniform
-            slow_group = k & ~7;
-            T_group = T_start;
-            for (unsigned hh = hits & below_group; hh; hh &= hh - 1) T_group = slow_factor(s, __builtin_ctz(hh), fx, fy, lane_bits, T_group);
-          }
-          Tk = T_group;
-          for (unsigned hh = hits & ((1u << k) - 1u) & ~below_group; hh; hh &= hh - 1) Tk = slow_factor(s, __builtin_ctz(hh), fx, fy, lane_bits, Tk);
-          incl = Tk * anti;
-        }
-        const bool keep = in & (incl != 0.0f);                // dropped when the inclusive product is exactly 0 (gs_model.py:560)
-        Tn = in ? Tk : Tn;
-        const float tg = keep ? Tk * gv : 0.0f;
-        float c = g0 * co.x + g1 * co.y + g2 * co.z;         // dL/dI . l
-        if (DEPTH) c += gz * co.w;                            // + dL/dD z
-        const float d = c - R;
+  float* const row_slot = &s_part[0][(p.w * 4 + (lane >> 4)) * kRowSlots + ((lane & 2) ? 4 : 0) + ((lane & 4) ? 2 : 0) + ((lane & 8) ? 1 : 0)];
+  if (DEPTH && da.tile_bg) tile_sum3(g0 * p.T_N, g1 * p.T_N, g2 * p.T_N, da.tile_bg + 3 * (i64)p.tile);
+  walk_back<DEPTH>(
+      a, da, s, p,
+      [&](int k, float op, float dx, float /*dy*/, float tg, float d) {
         float r_o = tg * d;
-        const float wgt = tg * ge.z;                            // T o g (gs_model.py:500 without l)
+        const float wgt = tg * op;                              // T o g (gs_model.py:500 without l)
         float r_c = wgt * d;
         float r_l0 = g0 * wgt, r_l1 = g1 * wgt, r_l2 = g2 * wgt;
         float r_cx = r_c * dx;
         float r_xx = r_cx * dx;
-        R = keep ? R + og * d : R;                              // R_{k-1} = R_k + a_k (c_k - R_k)
-        const int kc = k;
         // Seven 16-lane row sums by a transposed butterfly: at each step a lane keeps half of its values and hands the
         // other half to its partner, so the live registers halve.  Partners: 15-i, 7-i (within each half), i^2, i^1;
         // afterwards lane i holds the row sum of value ((i>>1)&1)*4 + ((i>>2)&1)*2 + ((i>>3)&1) (slot 7 is a dummy).
@@ -425,48 +237,32 @@ __device__ __forceinline__ void blend_bwd_tile(const BlendArgs& a, const int* __
             : "v"(q0), "v"(q1), "v"(q2), "v"(q3));
         const float o0 = xchg_sum<0x4e>(b1, p0, p1);
         const float tot = o0 + dpp_f<0xb1, 0xf>(0.0f, o0);
-        row_slot[kc * kPartStride] = tot;  // lanes i and i^1 store the same word
-      }
-    }
-    };
-    // two copies of the loop, chosen per chunk: the common one carries nothing of the other's (with one loop and the test inside,
-    // the common path ran 2-6 % slower after the slow one grew its per-group product)
-    if (__ballot(T_start != 0.0f) == 0ull) {
-      // every pixel of the strip enters the chunk behind an exact zero: T_k = 0 throughout, every term is 0 and R does not
-      // move — the wave hands the fold its zeros and goes on (a scene that crowds one region has half its pairs there)
-      for (unsigned hz = hits; hz; hz &= hz - 1) row_slot[__builtin_ctz(hz) * kPartStride] = 0.0f;
-    } else if (slow) {
-      walk_chunk(std::true_type{});
-    } else {
-      walk_chunk(std::false_type{});
-    }
-    __syncthreads();
-    // one thread per entry: add the 16 pixel rows in fixed order, write the entry's Gaussian-major slot
-    for (int j = threadIdx.x; j < cnt; j += 256) {
-      const i64 g = a.tile_list[base + j];
-      const int4 bx = s.box[j];
-      const int ntx = ((bx.x + bx.z) >> 4) - (bx.x >> 4) + 1;
-      const i64 e = (i64)tile_off[g] + (i64)(tty - (bx.y >> 4)) * ntx + (ttx - (bx.x >> 4));
-      float* out = partial + e * kVals;
-      const float my = s.geo[j].y;
-      float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f, cx = 0.0f, cy = 0.0f, xx = 0.0f, xy = 0.0f, yy = 0.0f, zz = 0.0f;
+        row_slot[k * kPartStride] = tot;  // lanes i and i^1 store the same word
+      },
+      [&](unsigned hits) {
+        for (unsigned hz = hits; hz; hz &= hz - 1) row_slot[__builtin_ctz(hz) * kPartStride] = 0.0f;
+      },
+      [&](int j, int entry) {
+        // add the 16 pixel rows in fixed order
+        float* out = partial + entry_slot(a, tile_off, entry, s.box[j], p.ttx, p.tty) * kVals;
+        const float my = s.geo[j].y;
+        float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f, o3 = 0.0f, cx = 0.0f, cy = 0.0f, xx = 0.0f, xy = 0.0f, yy = 0.0f, zz = 0.0f;
 #pragma unroll
-      for (int wv = 0; wv < 4; ++wv) {
-        if (!((s.hits[wv][0] >> j) & 1ull)) continue;  // that wave never wrote its rows for this entry
+        for (int wv = 0; wv < 4; ++wv) {
+          if (!((s.hits[wv][0] >> j) & 1ull)) continue;  // that wave never wrote its rows for this entry
 #pragma unroll
-        for (int r = 4 * wv; r < 4 * wv + 4; ++r) {
-          const float* d = &s_part[j][r * kRowSlots];
-          const float dy = (float)(tty * kTile + r) - my;  // constant along the pixel row
-          o0 += d[0]; o1 += d[1]; o2 += d[2]; o3 += d[3];
-          cx += d[5]; cy += dy * d[4];
-          xx += d[6]; xy += dy * d[5]; yy += dy * dy * d[4];
-          if (DEPTH) zz += d[7];
+          for (int r = 4 * wv; r < 4 * wv + 4; ++r) {
+            const float* d = &s_part[j][r * kRowSlots];
+            const float dy = (float)(p.tty * kTile + r) - my;  // constant along the pixel row
+            o0 += d[0]; o1 += d[1]; o2 += d[2]; o3 += d[3];
+            cx += d[5]; cy += dy * d[4];
+            xx += d[6]; xy += dy * d[5]; yy += dy * dy * d[4];
+            if (DEPTH) zz += d[7];
+          }
         }
-      }
-      out[0] = o0; out[1] = o1; out[2] = o2; out[3] = o3; out[4] = cx; out[5] = cy; out[6] = xx; out[7] = xy; out[8] = yy;
-      if (DEPTH) out[9] = zz;
-    }
-  }
+        out[0] = o0; out[1] = o1; out[2] = o2; out[3] = o3; out[4] = cx; out[5] = cy; out[6] = xx; out[7] = xy; out[8] = yy;
+        if (DEPTH) out[9] = zz;
+      });
 }
 
 __global__ __launch_bounds__(256) void k_blend_bwd(const BlendArgs a, const int* __restrict__ tile_off,
@@ -482,56 +278,16 @@ __global__ __launch_bounds__(256) void k_blend_bwd_depth(const BlendArgs a, cons
   blend_bwd_tile<true>(a, tile_off, t_ckpt, grad_image, partial, da);
 }
 
-// per Gaussian: sum its tile slots in order, expand the moments into the four gradients.
-// A Gaussian whose box covers many tiles (a background splat over the whole frame: 8 100 slots of 9 values) is not left to one
-// thread — 73 000 dependent loads, 1.1 ms for twenty of them while the rest of the launch takes 0.04 — but summed by its whole
-// wave: lane l takes slots e0 + l, e0 + l + 64, ... in order, and the 64 partial sums are added in a fixed butterfly.  Which
-// Gaussians go that way depends on their slot count alone, so the result is the same from run to run.
-constexpr int kReduceWide = 128;  // tile slots from which a Gaussian is summed by the wave
+
+// per Gaussian: sum its tile slots in order (reduce_slots of gcp_blend_shared.hpp), expand the moments into the four gradients.
 template <int NV>
 __device__ __forceinline__ void grad_reduce(const float* __restrict__ partial, const int* __restrict__ tile_off,
                                             const int* __restrict__ tile_start, int n_tiles, const float* __restrict__ vinv, i64 n,
                                             i64 capacity, float* grad_mean, float* grad_vinv, float* grad_opacity, float* grad_l,
                                             float* grad_z) {
   const i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  float r[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) r[v] = 0.0f;
-  // Only slots the blend kernel wrote are summed: a Gaussian's entries [tile_off[g], tile_off[g+1]) count iff they lie
-  // inside what the binning LISTED (tile_start[n_tiles] entries: everything with exact binning; with a capture-safe
-  // capacity the Gaussians that fit; nothing at all when the int32 prefix sums wrapped at > 2^31 entries — the offsets
-  // behind the wrap are negative or decreasing, and even the ones before it point at slots nobody wrote).  Zeros otherwise.
-  const i64 listed = min((i64)tile_start[n_tiles], capacity);
-  i64 e0 = 0, e1 = 0;
-  if (g < n) {
-    e0 = tile_off[g];
-    e1 = tile_off[g + 1];
-    if (e0 < 0 || e1 < e0 || e1 > listed) e1 = e0 < 0 ? 0 : e0;
-    if (e0 < 0) e0 = 0;
-  }
-  const bool wide = e1 - e0 >= kReduceWide;
-  if (!wide) {
-    for (i64 e = e0; e < e1; ++e)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) r[v] += partial[e * NV + v];
-  }
-  for (unsigned long long todo = __ballot(wide); todo; todo &= todo - 1ull) {  // wave-uniform: one wide Gaussian at a time
-    const int owner = __builtin_ctzll(todo);
-    const i64 f0 = (i64)__builtin_amdgcn_readlane((int)e0, owner), f1 = (i64)__builtin_amdgcn_readlane((int)e1, owner);  // (entries < 2^31)
-    float p[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) p[v] = 0.0f;
-    for (i64 e = f0 + lane; e < f1; e += 64)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) p[v] += partial[e * NV + v];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      float t = p[v];
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);  // a fixed butterfly: every lane ends with the same sum
-      if (lane == owner) r[v] = t;
-    }
-  }
+  const SlotSums<NV> sums = reduce_slots<SlotSums<NV>>(partial, tile_off, tile_start, n_tiles, g, n, capacity);
+  const float* r = sums.v;
   if (g >= n) return;
   const float A = vinv[4 * g], B = vinv[4 * g + 1], C = vinv[4 * g + 2], D = vinv[4 * g + 3];
   grad_opacity[g] = r[0];

@@ -14,48 +14,23 @@
 //                     four rows) and parks the pair in LDS at [entry][wave]; after every staged chunk one thread per entry
 //                     folds the waves that hit it, in wave order, and writes the entry's Gaussian-major slot (the slot
 //                     k_blend_bwd writes its partial sums to).
-//   k_contrib_reduce  one thread per Gaussian: the maximum and the in-order sum of its slots; a Gaussian with 128 slots or
-//                     more is taken by its whole wave, as in k_grad_reduce.
+//   k_contrib_reduce  one thread per Gaussian: the maximum and the in-order sum of its slots (reduce_slots, as k_grad_reduce: a
+//                     Gaussian with 128 slots or more is taken by its whole wave).
 // No float atomics: a maximum is exact in any order and every sum is taken in a fixed order => the same bits on every run.
-// gcp_blend.hip is not touched: the record staged here is leaner (no colour) and carries the parked pairs.
+// The staging, the slot address and the slot reduction are those of gcp_blend_shared.hpp; the record staged is its common part
+// (no colour) with the parked pairs added.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gcp_tiles.hpp"
+#include "gcp_blend_shared.hpp"
 
 namespace {
 using namespace gcp;
 
-struct ContribStaged {
-  int4 box[kStage];     // x0, y0, x1-x0, y1-y0 (clamped to the image): the fold's slot arithmetic
-  float4 geo[kStage];   // mx, my, opacity, box mask as bits (0-15: tile columns inside the box, 16-31: tile rows)
-  float4 vin[kStage];   // Λ' = -0.5*log2(e) * Λ, a b c d
-  // hits[w][c]: bit j set = staged entry 64*c + j reaches into the four pixel rows of wave w (as in gcp_blend.hip)
-  unsigned long long hits[4][kStage / 64];
+struct ContribStaged : Staged<kStage> {  // the common record, no colour: box, geo, vin (a b c d), hits
   float2 part[kStage][4];  // [entry][wave]: (max, sum) of w over the wave's 64 pixels; written only where hits says so
 };
-
-__device__ __forceinline__ void stage_contrib(const BlendArgs& a, ContribStaged& s, int first, int cnt, int tile_x0, int tile_y0) {
-  for (int j = threadIdx.x; j < cnt; j += blockDim.x) {
-    const i64 g = a.tile_list[first + j];
-    Box b;
-    load_box(a.start, a.end, g, a.W, a.H, b);
-    s.box[j] = make_int4(b.x0, b.y0, b.x1 - b.x0, b.y1 - b.y0);
-    const int c0 = max(b.x0 - tile_x0, 0), c1 = min(b.x1 - tile_x0, kTile - 1);
-    const int r0 = max(b.y0 - tile_y0, 0), r1 = min(b.y1 - tile_y0, kTile - 1);
-    const unsigned cm = (c1 >= c0) ? ((2u << c1) - (1u << c0)) : 0u;
-    const unsigned rm = (r1 >= r0) ? ((2u << r1) - (1u << r0)) : 0u;
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {  // entries j of one 64-lane staging wave form one word per target wave
-      const unsigned long long touched = __ballot(((rm >> (4 * w2)) & 0xfu) != 0u);
-      if ((threadIdx.x & 63) == 0) s.hits[w2][j >> 6] = touched;
-    }
-    s.geo[j] = make_float4(a.mean[2 * g], a.mean[2 * g + 1], a.opacity[g], __uint_as_float(cm | (rm << 16)));
-    constexpr float kS = -0.5f * 1.44269504088896341f;  // the forward blend's pre-scaling, product by product
-    s.vin[j] = make_float4(kS * a.vinv[4 * g], kS * a.vinv[4 * g + 1], kS * a.vinv[4 * g + 2], kS * a.vinv[4 * g + 3]);
-  }
-}
 
 // Maximum and sum of a value over the wave in a fixed order, valid in lane 63: an inclusive scan along each 16-lane DPP
 // row (= one pixel row of the tile), then row 0 into row 1 and row 2 into row 3, then row 1 into row 3.  A lane without a
@@ -93,7 +68,7 @@ __global__ __launch_bounds__(256) void k_contrib_tile(const BlendArgs a, const i
   for (int base = first; base < last; base += kStage) {
     const int cnt = __builtin_amdgcn_readfirstlane(min(kStage, last - base));  // scalar loop bound
     __syncthreads();
-    stage_contrib(a, s, base, cnt, ttx * kTile, tty * kTile);
+    stage_entries<false, false>(a, s, base, cnt, ttx * kTile, tty * kTile);
     __syncthreads();
     const int chunks = (cnt + 63) >> 6;
     for (int c = 0; c < chunks; ++c) {
@@ -132,10 +107,7 @@ __global__ __launch_bounds__(256) void k_contrib_tile(const BlendArgs a, const i
     __syncthreads();
     // one thread per entry: the waves that hit it in wave order, into the entry's Gaussian-major slot
     for (int j = threadIdx.x; j < cnt; j += 256) {
-      const i64 g = a.tile_list[base + j];
-      const int4 bx = s.box[j];
-      const int ntx = ((bx.x + bx.z) >> 4) - (bx.x >> 4) + 1;
-      const i64 e = (i64)tile_off[g] + (i64)(tty - (bx.y >> 4)) * ntx + (ttx - (bx.x >> 4));
+      const i64 e = entry_slot(a, tile_off, base + j, s.box[j], ttx, tty);
       float mx = 0.0f, sm = 0.0f;
 #pragma unroll
       for (int wv = 0; wv < 4; ++wv) {
@@ -149,52 +121,32 @@ __global__ __launch_bounds__(256) void k_contrib_tile(const BlendArgs a, const i
   }
 }
 
-// per Gaussian: the maximum and the in-order sum of its tile slots.  Only slots k_contrib_tile wrote are read — the rule
-// of k_grad_reduce (gcp_blend.hip): a Gaussian's entries [tile_off[g], tile_off[g+1]) count iff they lie inside what the
-// binning LISTED (tile_start[n_tiles] entries, at most the capacity); offsets that wrapped or are inverted give zeros.
-// A Gaussian with kWide slots or more is taken by its whole wave: lane l folds slots e0 + l, e0 + l + 64, ... in order and
-// the 64 partial results meet in a fixed butterfly.  Which Gaussians go that way depends on their slot count alone.
-constexpr int kWide = 128;
+// (max, sum) per slot; the maximum of non-negative values from 0
+struct SlotMaxSum {
+  float mx = 0.0f, sm = 0.0f;
+  __device__ __forceinline__ void add(const float2* __restrict__ slot, i64 e) {
+    const float2 p = slot[e];
+    mx = fmaxf(mx, p.x);
+    sm += p.y;
+  }
+  __device__ __forceinline__ void wave_all() {
+    for (int o = 32; o > 0; o >>= 1) {
+      mx = fmaxf(mx, __shfl_xor(mx, o));
+      sm += __shfl_xor(sm, o);
+    }
+  }
+};
+
+// per Gaussian: the maximum and the in-order sum of its tile slots (reduce_slots of gcp_blend_shared.hpp: only slots
+// k_contrib_tile wrote are read)
 __global__ __launch_bounds__(256) void k_contrib_reduce(const float2* __restrict__ slot, const int* __restrict__ tile_off,
                                                         const int* __restrict__ tile_start, int n_tiles, i64 n, i64 capacity,
                                                         float* __restrict__ w_max, float* __restrict__ w_sum) {
   const i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63;
-  const i64 listed = min((i64)tile_start[n_tiles], capacity);
-  i64 e0 = 0, e1 = 0;
-  if (g < n) {
-    e0 = tile_off[g];
-    e1 = tile_off[g + 1];
-    if (e0 < 0 || e1 < e0 || e1 > listed) e1 = e0 < 0 ? 0 : e0;
-    if (e0 < 0) e0 = 0;
-  }
-  float mx = 0.0f, sm = 0.0f;
-  const bool wide = e1 - e0 >= kWide;
-  if (!wide) {
-    for (i64 e = e0; e < e1; ++e) {
-      const float2 p = slot[e];
-      mx = fmaxf(mx, p.x);
-      sm += p.y;
-    }
-  }
-  for (unsigned long long todo = __ballot(wide); todo; todo &= todo - 1ull) {  // wave-uniform: one wide Gaussian at a time
-    const int owner = __builtin_ctzll(todo);
-    const i64 f0 = (i64)__builtin_amdgcn_readlane((int)e0, owner), f1 = (i64)__builtin_amdgcn_readlane((int)e1, owner);  // (entries < 2^31)
-    float pm = 0.0f, ps = 0.0f;
-    for (i64 e = f0 + lane; e < f1; e += 64) {
-      const float2 p = slot[e];
-      pm = fmaxf(pm, p.x);
-      ps += p.y;
-    }
-    for (int o = 32; o > 0; o >>= 1) {  // a fixed butterfly: every lane ends with the same pair
-      pm = fmaxf(pm, __shfl_xor(pm, o));
-      ps += __shfl_xor(ps, o);
-    }
-    if (lane == owner) { mx = pm; sm = ps; }
-  }
+  const SlotMaxSum r = reduce_slots<SlotMaxSum>(slot, tile_off, tile_start, n_tiles, g, n, capacity);
   if (g >= n) return;
-  w_max[g] = mx;
-  w_sum[g] = sm;
+  w_max[g] = r.mx;
+  w_sum[g] = r.sm;
 }
 
 }  // namespace

@@ -215,15 +215,14 @@ def _blend_forward(bins, params, with_checkpoints, depth=None, background=None, 
     return (image, *maps, ckpt)
 
 
-def _blend_backward(bins, params, t_ckpt, grad_image, forward_name, depth=None, background=None, grad_maps=None, background_grad=False):
-    """Both backward entry points; grad_maps None: colour only, else (grad_depth, grad_alpha) of the depth call
-    -> (grad_mean, grad_variance_inverse, grad_opacity, grad_l_d[, grad_depth, grad_background])."""
-    with_depth = grad_maps is not None
-    start, end, mean_f, vinv, op, col = _params(*params)
+def _backward_inputs(bins, start, t_ckpt, grad_image, forward_name, depth, background, grad_maps):
+    """What the backward and the absolute gradient take besides the per-Gaussian arguments, validated; grad_maps None: colour
+    only (z, bg None and maps empty), else (grad_depth, grad_alpha) of the depth call, where grad_image None means zero.
+    -> (lib, z, bg, grad_image, [grad_depth, grad_alpha] or [], t_ckpt)."""
     dev = start.device
-    n = bins.n_gauss
     shape = (bins.height + 1, bins.width + 1)
-    if with_depth:
+    z = bg = None
+    if grad_maps is not None:
         z, bg = _depth_args(depth, background, start.size(0), dev)
         if grad_image is None:
             grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
@@ -239,6 +238,17 @@ def _blend_backward(bins, params, t_ckpt, grad_image, forward_name, depth=None, 
     ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
     _require(ck.numel() >= _checkpoint_floats(lib, bins),
              f"t_ckpt: too small for these bins (pass what {forward_name}(..., with_checkpoints=True) returned)")
+    return lib, z, bg, gimg, maps, ck
+
+
+def _blend_backward(bins, params, t_ckpt, grad_image, forward_name, depth=None, background=None, grad_maps=None, background_grad=False):
+    """Both backward entry points; grad_maps None: colour only, else (grad_depth, grad_alpha) of the depth call
+    -> (grad_mean, grad_variance_inverse, grad_opacity, grad_l_d[, grad_depth, grad_background])."""
+    with_depth = grad_maps is not None
+    start, end, mean_f, vinv, op, col = _params(*params)
+    dev = start.device
+    n = bins.n_gauss
+    lib, z, bg, gimg, maps, ck = _backward_inputs(bins, start, t_ckpt, grad_image, forward_name, depth, background, grad_maps)
     grads = [torch.empty(n, *tail, dtype=torch.float32, device=dev) for tail in ((2,), (2, 2), (1,), (3,))]  # mean, vinv, opacity, l_d
     name = "gcp_blend_backward_depth" if with_depth else "gcp_blend_backward"
     with torch.cuda.device(dev):
@@ -327,23 +337,7 @@ def _blend_absgrad(bins, params, t_ckpt, grad_image, forward_name, depth=None, b
     dev = start.device
     n = bins.n_gauss
     _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
-    shape = (bins.height + 1, bins.width + 1)
-    if with_depth:
-        z, bg = _depth_args(depth, background, n, dev)
-        if grad_image is None:
-            grad_image = torch.zeros(*shape, 3, dtype=torch.float32, device=dev)
-    gimg = _dev_tensor(grad_image, "grad_image", torch.float32)
-    _require(tuple(gimg.shape) == shape + (3,), f"grad_image: expected shape {shape + (3,)}")
-    maps = []
-    for t, name in zip(grad_maps or (), ("grad_depth", "grad_alpha")):
-        if t is not None:
-            t = _dev_tensor(t, name, torch.float32)
-            _require(tuple(t.shape) == shape, f"{name}: expected shape {shape}")
-        maps.append(t)
-    lib = _lib.load()
-    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
-    _require(ck.numel() >= _checkpoint_floats(lib, bins),
-             f"t_ckpt: too small for these bins (pass what {forward_name}(..., with_checkpoints=True) returned)")
+    lib, z, bg, gimg, maps, ck = _backward_inputs(bins, start, t_ckpt, grad_image, forward_name, depth, background, grad_maps)
     if out is None:
         absgrad = torch.empty(n, 2, dtype=torch.float32, device=dev)
     else:

@@ -156,7 +156,7 @@ def test_from_ply_passes_the_option_through(tmp_path):
 
 def test_absgrad_kernels_use_no_scratch(tmp_path):
     """k_absgrad_tile / k_absgrad_tile_depth at the occupancy of k_blend_bwd or better (<= 80 VGPRs: six waves per SIMD, the
-    bar tests/test_cabi.py sets for the blend kernels; measured 48 / 50: eight), k_absgrad_reduce at eight (<= 64; measured
+    bar tests/test_cabi.py sets for the blend kernels; measured 44 / 44: eight), k_absgrad_reduce at eight (<= 64; measured
     22).  No scratch, no spills."""
     from simplegaussiansplat_tk71_amd import _build
 
