@@ -31,6 +31,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --densify mcmc --cap-max 4000 --adam sparse
                                                              # Adam only on the rows a camera of the batch saw, all five
                                                              # tensors in one launch (--adam fused: the same launch, every row)
+    python examples/train_cameras.py --distortion-reg 100 --distortion-from 300
+                                                             # from iteration 300 the loss gains 100 * the mean per-pixel depth
+                                                             # distortion (Mip-NeRF 360 / 2DGS): pulls each ray's weights together
     python examples/train_cameras.py --test-every 8 --eval-every 100 --eval-json eval.json
                                                              # hold out every 8th camera (sorted by name, the llffhold convention),
                                                              # report PSNR / SSIM / L1 on them every 100 iterations and at the end
@@ -100,7 +103,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
-          screen_grad="signed"):
+          screen_grad="signed", distortion_reg=0.0, distortion_from=0):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -140,6 +143,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     over black under "random" — no colour is drawn for it), `gs_model.gather_metrics` collects the ranks' shares, and rank 0
     logs the means and appends to the list `evals` a record {"iteration", "split": "test", "views", "gaussians", "psnr",
     "ssim", "l1", "per_image": {name: {"psnr", "ssim", "l1"}}}, psnr / ssim / l1 being the means of the per-image values.
+    `distortion_reg` L > 0: from iteration `distortion_from` on, the step renders through `model.render(distortion=True)` (over
+    black where no `background` is set) and the loss gains L * mean(distortion map) — the depth distortion loss of Mip-NeRF 360 /
+    2DGS (`cuda_kernel.render`), in units of camera-space depth; the weight is not tuned here.  With L = 0 (the default) no
+    step changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -215,18 +222,26 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             idx = order[b:b + batch_size].to(dev)
             mine = idx[rank::world]
             if mine.numel():
-                if background is None:
+                distort = distortion_reg > 0 and iteration >= distortion_from
+                dist = None
+                if background is None and not distort:
                     images, kept, grad_iter = model(P[mine], K[mine], wh[mine], mine.tolist())
                     target = targets[torch.tensor(kept, device=dev)]
                 else:
-                    bg = torch.rand(3, device=dev) if isinstance(background, str) else torch.as_tensor(background, dtype=torch.float32,
-                                                                                                          device=dev)
-                    images, _, _, kept, grad_iter = model.render(P[mine], K[mine], wh[mine], background=bg, image_sample=mine.tolist())
+                    bg = None
+                    if background is not None:
+                        bg = torch.rand(3, device=dev) if isinstance(background, str) else torch.as_tensor(background, dtype=torch.float32,
+                                                                                                              device=dev)
+                    images, *maps, kept, grad_iter = model.render(P[mine], K[mine], wh[mine], background=bg, image_sample=mine.tolist(),
+                                                                  distortion=distort)
+                    dist = maps[2] if distort else None
                     sel = torch.tensor(kept, device=dev)
                     target = targets[sel]
-                    if target_alpha is not None:
+                    if bg is not None and target_alpha is not None:
                         target = target + (1 - target_alpha[sel]) * bg[None, :, None, None]
                 loss = gm.splat_loss(images, target, loss_lamda) * (mine.numel() / idx.numel())
+                if dist is not None:  # the geometric regulariser: the mean per-pixel depth distortion of this rank's share
+                    loss = loss + distortion_reg * dist.mean() * (mine.numel() / idx.numel())
                 if densify == "mcmc":  # the regularisers that let opacities die and keep scales small; the whole term on every rank's share
                     loss = loss + (opacity_reg * torch.sigmoid(model.opacity).mean()
                                    + scale_reg * torch.exp(model.variance_scale).mean()) * (mine.numel() / idx.numel())
@@ -294,7 +309,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     return model, losses
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--colmap", default=None, help="COLMAP root (sparse/0/*.bin + images/); default: synthetic scene")
     ap.add_argument("--gaussians", type=int, default=3000)
@@ -345,6 +360,14 @@ if __name__ == "__main__":
     ap.add_argument("--eval-every", type=int, default=0, metavar="I",
                     help="with --test-every: PSNR / SSIM / L1 on the held-out cameras every I iterations (0: only after the last step)")
     ap.add_argument("--eval-json", default=None, metavar="PATH", help="write the evaluation records (rank 0) as a JSON list")
+    ap.add_argument("--distortion-reg", type=float, default=0.0, metavar="L",
+                    help="weight of the mean per-pixel depth distortion (Mip-NeRF 360 / 2DGS) in the loss (0: off; not tuned here)")
+    ap.add_argument("--distortion-from", type=int, default=0, metavar="I", help="with --distortion-reg: the first iteration that carries the term")
+    return ap
+
+
+if __name__ == "__main__":
+    ap = build_parser()
     a = ap.parse_args()
     if (a.eval_every or a.eval_json) and not a.test_every:
         ap.error("--eval-every and --eval-json need --test-every N with N > 0")
@@ -376,7 +399,7 @@ if __name__ == "__main__":
                       antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg,
                       prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam,
                       test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names,
-                      screen_grad=a.screen_grad)
+                      screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -857,6 +857,36 @@ int gcp_blend_absgrad_depth(const int32_t* start_xy, const int32_t* end_xy, cons
                             const float* grad_depth_map, const float* grad_alpha_map, float* absgrad, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* Depth distortion of one camera (gcp_distort.hip; the distortion loss of Mip-NeRF 360, 2DGS, gsplat's distloss).  Per pixel
+ * p, over its kept pairs k = 1..n front to back with the pair rule of gcp_blend_forward to the letter (w_k = T_k o_k g_k, a
+ * pair whose inclusive product is exactly 0 is dropped: w = 0, no gradient), z_k = depth[k] the per-Gaussian scalar
+ * gcp_blend_forward_depth takes, A_k = sum_{j<=k} w_j and B_k = sum_{j<=k} w_j z_j:
+ *   dist(p) = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})      ( = sum_{i>j} 2 w_i w_j (z_i - z_j) )
+ * — the order-based form: it equals sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list order, as the camera
+ * depth the list is sorted by is (ties contribute 0).  Like the depth map it is not divided by alpha and is in units of z.
+ * The forward writes three maps of (H+1)(W+1) floats: dist, a_n = A_n and b_n = B_n (a_n is NOT the alpha map: behind an
+ * exactly opaque layer alpha = 1 while A_n is the sum in front of the dropped pair).  n_gauss == 0: the maps are zeroed.
+ * The backward takes them back with t_ckpt of a checkpointed blend forward ON THE SAME BINS and G = grad_dist = dL/d dist;
+ * with the inclusive suffix sums SA_k, SB_k of w and w z it runs the blend backward's own recursion on
+ *   c_k = 2 G [ z_k (A_n - 2 SA_k) - (B_n - 2 SB_k) ],   dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+ * (R = 0 behind the list, R_{k-1} = R_k + a_k (c_k - R_k), dL/do_k = T_k g_k (c_k - R_k), common = T_k a_k (c_k - R_k)) and
+ * WRITES grad_mean [N,2], grad_vinv [N,4], grad_opacity [N], grad_depth [N]: the recursion is linear in c, so these add to
+ * the gradients of gcp_blend_backward_depth.  0 for an empty box and for a Gaussian the binning did not list.
+ * n_gauss == 0: nothing is touched; n_tile_pairs == 0: the four outputs are zeroed.  No atomics: two calls give the same
+ * bits.  No stream synchronise, no read-back, no allocation.
+ * ws: gcp_blend_distort_backward_workspace_bytes(K) (28 bytes per entry). */
+int gcp_blend_distort_forward(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                              const float* opacity, const float* depth, int64_t n_gauss, int32_t width, int32_t height,
+                              const int32_t* tile_start, const int32_t* tile_list, float* dist_map, float* a_n, float* b_n,
+                              void* stream);
+size_t gcp_blend_distort_backward_workspace_bytes(int64_t n_tile_pairs);
+int gcp_blend_distort_backward(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                               const float* opacity, const float* depth, int64_t n_gauss, int32_t width, int32_t height,
+                               const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start,
+                               const int32_t* tile_list, const float* t_ckpt, const float* a_n, const float* b_n,
+                               const float* grad_dist, float* grad_mean, float* grad_vinv, float* grad_opacity,
+                               float* grad_depth, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@
 //                trade-offs and stay in their files.
 //   slots        the Gaussian-major slot of a (tile, Gaussian) entry, and the per-Gaussian reduction over a Gaussian's slots
 //                with the accumulator as a parameter.
+// gcp_distort.hip (depth distortion) runs on all three: its record carries z instead of the colour, and its c_k comes from a
+// hook of walk_back that compiles out of the other kernels.
 // Everything is in an anonymous namespace, per translation unit, as BlendArgs in gcp_tiles.hpp: the kernels' symbol names spell
 // their parameter types, and profiles and tests are read by those names.
 #pragma once
@@ -57,7 +59,7 @@ struct DepthArgs {
 // What every tile kernel stages per list entry; the records below add what only some of them read.
 template <int STAGE>
 struct Staged {
-  static constexpr bool kHasCol = false, kHasRaw = false;
+  static constexpr bool kHasCol = false, kHasRaw = false, kHasZ = false;
   int4 box[STAGE];     // x0, y0, x1-x0, y1-y0 (clamped to the image)
   float4 geo[STAGE];   // mx, my, opacity, box mask as bits (0-15: tile columns inside the box, 16-31: tile rows)
   float4 vin[STAGE];   // Λ' = -0.5*log2(e) * Λ, Λ = [[a,b],[c,d]]: a b c d (forward walks) or a, b + c, d, - (back-to-front walk)
@@ -74,6 +76,12 @@ template <int STAGE>
 struct StagedColRaw : StagedCol<STAGE> {  // + Λ itself: the absgrad
   static constexpr bool kHasRaw = true;
   float4 raw[STAGE];   // A B C D
+};
+
+template <int STAGE>
+struct StagedZ : Staged<STAGE> {  // + the depth alone: the distortion
+  static constexpr bool kHasZ = true;
+  float z[STAGE];
 };
 
 template <bool QUAD3, bool DEPTH, class S>
@@ -106,6 +114,7 @@ __device__ __forceinline__ void stage_entries(const BlendArgs& a, S& s, int firs
     s.vin[j] = QUAD3 ? make_float4(kS * A, kS * B + kS * C, kS * D, 0.0f) : make_float4(kS * A, kS * B, kS * C, kS * D);
     if constexpr (S::kHasRaw) s.raw[j] = make_float4(A, B, C, D);
     if constexpr (S::kHasCol) s.col[j] = make_float4(a.l_d[3 * g], a.l_d[3 * g + 1], a.l_d[3 * g + 2], DEPTH ? z[g] : 0.0f);
+    if constexpr (S::kHasZ) s.z[j] = z[g];
   }
 }
 
@@ -230,7 +239,8 @@ struct WalkPixel {
   float R;                  // R behind the list: 0, or the absorbing layer's (DepthArgs)
 };
 
-template <bool DEPTH>
+// IMAGE false: no dL/dI is read (g0 = g1 = g2 = 0; grad_image may be null) — the distortion's walk
+template <bool DEPTH, bool IMAGE = true>
 __device__ __forceinline__ WalkPixel walk_pixel(const BlendArgs& a, const float* __restrict__ t_ckpt,
                                                 const float* __restrict__ grad_image, const DepthArgs& da) {
 #pragma clang fp contract(fast)  // as in walk_back
@@ -245,7 +255,7 @@ __device__ __forceinline__ WalkPixel walk_pixel(const BlendArgs& a, const float*
   p.first = a.tile_start[p.tile];
   p.last = a.tile_start[p.tile + 1];
   p.g0 = p.g1 = p.g2 = 0.0f;
-  if (p.px <= a.W && p.py <= a.H) {
+  if (IMAGE && p.px <= a.W && p.py <= a.H) {
     const i64 o = ((i64)p.py * (a.W + 1) + p.px) * 3;
     p.g0 = grad_image[o]; p.g1 = grad_image[o + 1]; p.g2 = grad_image[o + 2];
   }
@@ -275,8 +285,16 @@ __device__ __forceinline__ WalkPixel walk_pixel(const BlendArgs& a, const float*
 //   zero(hits)                        hand the fold zeros for the wave's entries (the set bits)
 // and per chunk, after a barrier, one thread per entry:
 //   fold(j, entry)                    staged entry j = list entry `entry`, into its Gaussian-major slot (entry_slot)
-template <bool DEPTH, class S, class Body, class Zero, class Fold>
-__device__ __forceinline__ void walk_back(const BlendArgs& a, const DepthArgs& da, S& s, const WalkPixel& p, Body body, Zero zero, Fold fold) {
+// `hook` replaces c_k = dL/dI . l_k (+ dL/dD z_k) where the caller's c_k is not a fixed per-entry number but depends on the lane's
+// own state: with Hook::kOn the record needs no colour, and per entry, before the body,
+//   c_k = hook.c(s, k, w_k)           w_k = T_k o_k g_k (0 outside the box and for a dropped pair)
+// The default compiles out.
+struct NoHook {
+  static constexpr bool kOn = false;
+};
+template <bool DEPTH, class S, class Body, class Zero, class Fold, class Hook = NoHook>
+__device__ __forceinline__ void walk_back(const BlendArgs& a, const DepthArgs& da, S& s, const WalkPixel& p, Body body, Zero zero, Fold fold,
+                                          Hook&& hook = Hook{}) {
   // The blend kernels are VALU-issue bound: let a*b+c contract into v_fma_f32 here (the library is otherwise built
   // with -ffp-contract=off).  One rounding instead of two per contraction; results stay within the 1e-5 bar.
 #pragma clang fp contract(fast)
@@ -311,7 +329,8 @@ __device__ __forceinline__ void walk_back(const BlendArgs& a, const DepthArgs& d
         // straight-line for all 64 lanes; lanes outside the box / dropped pairs are zeroed with selects
         const float4 ge = s.geo[k];
         const float4 vi = s.vin[k];
-        const float4 co = s.col[k];
+        float4 co;
+        if constexpr (!std::decay_t<Hook>::kOn) co = s.col[k];
         const bool in = (__float_as_uint(ge.w) & lane_bits) == lane_bits;
         const float dx = fx - ge.x, dy = fy - ge.y;
         // (d Λ) d^T (gs_model.py:495) as a dx^2 + (b + c) dx dy + d dy^2
@@ -342,8 +361,13 @@ __device__ __forceinline__ void walk_back(const BlendArgs& a, const DepthArgs& d
         const bool keep = in & (incl != 0.0f);                // dropped when the inclusive product is exactly 0 (gs_model.py:560)
         Tn = in ? Tk : Tn;
         const float tg = keep ? Tk * gv : 0.0f;
-        float c = g0 * co.x + g1 * co.y + g2 * co.z;         // dL/dI . l
-        if (DEPTH) c += gz * co.w;                            // + dL/dD z
+        float c;
+        if constexpr (std::decay_t<Hook>::kOn) {
+          c = hook.c(s, k, tg * ge.z);
+        } else {
+          c = g0 * co.x + g1 * co.y + g2 * co.z;              // dL/dI . l
+          if (DEPTH) c += gz * co.w;                            // + dL/dD z
+        }
         const float d = c - R;
         body(k, ge.z, dx, dy, tg, d);
         R = keep ? R + og * d : R;                              // R_{k-1} = R_k + a_k (c_k - R_k)

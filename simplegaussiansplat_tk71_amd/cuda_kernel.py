@@ -64,6 +64,7 @@ __all__ = [
     "grad_cumsum_boxes",
     "custom_autograd_grouped_cumprod",
     "RenderDepth",
+    "RenderDistortion",
     "render",
     "contribution",
     "absgrad_buffer",
@@ -715,7 +716,54 @@ class RenderDepth(torch.autograd.Function):
                 g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
 
 
-def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None):
+class RenderDistortion(torch.autograd.Function):
+    """`RenderDepth` with a fourth output, the per-pixel depth distortion map (csrc/gcp_distort.hip, k_distort_fwd /
+    k_distort_bwd / k_distort_reduce on the bins and transmittance checkpoints of the blend); see `render(distortion=True)`.
+    Image, depth and alpha come from the same kernels as `RenderDepth`'s: the same bits.  The distortion's gradients are
+    computed in a walk of their own and added (the backward recursion is linear in c_k); when the loss does not use the map its
+    gradient arrives as None, no distortion kernel is launched and the gradients are `RenderDepth`'s bit for bit.  Capture-safe
+    and overflow-reporting under `tile_capacity` / `GraphedStep`.  The optional trailing `absgrad` buffer is filled from the
+    gradients of the THREE maps only: the regulariser's term is not part of the densification statistic."""
+
+    @staticmethod
+    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                *absgrad):
+        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
+        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
+        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
+        with torch.no_grad():
+            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                     l_d, depth, background, with_checkpoints=True)
+            dist, a_n, b_n = _raster.blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
+        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, a_n, b_n)
+        return image, dmap, alpha, dist
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_alpha, g_dist):
+        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, a_n, b_n), bins = _saved_with_bins(ctx)
+        want_bg = background is not None and ctx.needs_input_grad[9]
+        with torch.no_grad():
+            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
+                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
+                background, background_grad=want_bg)
+            if ctx.absgrad is not None:
+                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
+                                            g_depth, g_alpha, background, out=ctx.absgrad)
+            if g_dist is not None:
+                d_mean, d_vinv, d_op, d_z = _raster.blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                           depth, t_ckpt, a_n, b_n, g_dist)
+                g_mean += d_mean
+                g_vinv += d_vinv
+                g_op += d_op
+                g_z += d_z
+        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
+        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
+                g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
+
+
+def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None,
+           distortion=False):
     """Rasterise and blend one camera's depth-ordered Gaussians (the arguments of `custom_autograd_grouped_cumprod`, without
     boxsize / batch) -> (image (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), differentiable in mean (if float),
     variance_inverse, opacity, l_d, depth and background.
@@ -731,11 +779,20 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
     over the pixels in a fixed order (the same bits on every run).
     `absgrad`: None, or a float32 [N, 2] device tensor (`absgrad_buffer`) that `backward` fills with the absolute screen-space
     gradient of the three maps' gradients (`raster.blend_absgrad_depth`); not differentiable, and the gradients of the other
-    arguments are the same bits with and without it."""
+    arguments are the same bits with and without it.
+    `distortion=True` (`RenderDistortion`) -> (image, depth, alpha, dist): the first three bit for bit as without it, and
+      dist(p) = 2 sum_k w_k (z_k A_{k-1} - B_{k-1}),  A_k = sum_{j<=k} w_j,  B_k = sum_{j<=k} w_j z_j
+              = sum_{i>j} 2 w_i w_j (z_i - z_j)
+    over p's kept pairs front to back (a dropped pair has w = 0 and no gradient): the depth distortion of Mip-NeRF 360 / 2DGS
+    (gsplat's distloss) in its order-based form, equal to sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list
+    order — as the camera depth the list is sorted by is; ties contribute 0.  Like the depth map it is not divided by alpha and
+    is in units of z.  A loss that does not use `dist` launches no distortion kernel in backward and gets the gradients of the
+    three-map call bit for bit.  With `absgrad` given the buffer is filled from the three maps' gradients only: the
+    regulariser's term is not part of the densification statistic."""
+    fn = RenderDistortion if distortion else RenderDepth
     if absgrad is None:
-        return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
-    return RenderDepth.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
-                             absgrad)
+        return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
+    return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, absgrad)
 
 
 def contribution(startpoint, endpoint, mean, variance_inverse, opacity, image_width, image_height):

@@ -637,23 +637,26 @@ class GS_model_with_param(torch.nn.Module):
         out = out.reshape(-1, 3, h, w) if self.reference_layout else out.permute(0, 3, 1, 2).contiguous()
         return [out, names, grad_iter]
 
-    def render(self, P, K, wh, background=None, image_sample=None):
+    def render(self, P, K, wh, background=None, image_sample=None, distortion=False):
         """`forward` with the expected-depth and alpha maps and a background colour (`cuda_kernel.render`, whose
         docstring pins the definitions: depth = sum of the colour weights times the camera-space depth, NOT divided by
         alpha; alpha = 1 - the transmittance behind the pixel; image composited over `background`, a float[3] device tensor
         or None for black).  Returns [images (B, 3, H, W), depth (B, 1, H, W), alpha (B, 1, H, W), names, grad_iter], all
         maps after the same [1:, 1:] crop as `forward`; `names` are `image_sample`'s entries (default: camera indices) of the
-        cameras that see anything — the others are dropped, as in `forward`."""
+        cameras that see anything — the others are dropped, as in `forward`.
+        distortion=True: [images, depth, alpha, distortion (B, 1, H, W), names, grad_iter] — the per-pixel depth distortion
+        of `cuda_kernel.render(distortion=True)` (sum_{i>j} 2 w_i w_j (z_i - z_j) over the pixel's kept pairs, z the
+        camera-space depth the list is sorted by; not divided by alpha), cropped like the others; the first three maps are the
+        same bits as without it."""
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
         self._watch_centres(cams, width, height)
-        (images, depth, alpha), names = self._draw_cameras(
+        maps, names = self._draw_cameras(
             cams, range(P.shape[0]) if image_sample is None else image_sample,
             lambda cam: render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
-                               cam["depth"], width, height, background, cam.get("absgrad")))
-        images = images[:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
-        depth = depth[:, None, 1:, 1:].contiguous()
-        alpha = alpha[:, None, 1:, 1:].contiguous()
-        return [images, depth, alpha, names, grad_iter]
+                               cam["depth"], width, height, background, cam.get("absgrad"), distortion=distortion))
+        images = maps[0][:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
+        planes = [m[:, None, 1:, 1:].contiguous() for m in maps[1:]]  # depth, alpha[, distortion]
+        return [images, *planes, names, grad_iter]
 
     @torch.no_grad()
     def evaluate(self, P, K, wh, targets, background=None, batch_size=4, clamp=True):

@@ -1,6 +1,6 @@
 """Tile binning and fused alpha blending on the HIP library.
 
-Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_absgrad.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
+Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_absgrad.hip, gcp_distort.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
 (include/grouped_cumprod_hip.h).  Everything the reference does around its scan in
 `custom_autograd_grouped_cumprod` (reference: gs_model.py:598-663) happens in three launches here:
 bin (f2), blend forward (f1), blend backward (f1).  No CPU path.
@@ -374,6 +374,72 @@ def blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opac
     grad_alpha> (None: zero), the image composited over `background` (None: black) -> f32 [N, 2]."""
     return _blend_absgrad(bins, (startpoint, endpoint, mean, variance_inverse, opacity, l_d), t_ckpt, grad_image, "blend_forward_depth",
                           depth, background, (grad_depth, grad_alpha), out=out)
+
+
+def blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth):
+    """The per-pixel depth distortion on the bins `blend_forward_depth` paints (gcp_blend_distort_forward,
+    csrc/gcp_distort.hip; the distortion loss of Mip-NeRF 360 / 2DGS, gsplat's distloss) -> (dist, a_n, b_n), each
+    f32[H+1, W+1].  Per pixel, over its kept pairs k = 1..n front to back — the pair rule is the forward blend's: w_k = T_k o_k
+    g_k, a dropped pair (inclusive product exactly 0) has w = 0 and gets no gradient — with z_k = depth[k], A_k = sum_{j<=k} w_j
+    and B_k = sum_{j<=k} w_j z_j:
+        dist = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})   ( = sum_{i>j} 2 w_i w_j (z_i - z_j) )
+    the order-based form: it equals sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list order, as the camera
+    depth the list is sorted by is (ties contribute 0).  Like the depth map it is not divided by alpha and is in units of z.
+    a_n = A_n and b_n = B_n are what `blend_distort_backward` needs back: a_n is not the alpha map (behind an exactly opaque
+    layer alpha = 1, a_n is the sum in front of the dropped pair)."""
+    start, end, mean_f, vinv, op = _params(startpoint, endpoint, mean, variance_inverse, opacity)
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    z, _ = _depth_args(depth, None, n, dev)
+    lib = _lib.load()
+    shape = (bins.height + 1, bins.width + 1)
+    maps = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3)]
+    with torch.cuda.device(dev):
+        _lib.check(
+            lib.gcp_blend_distort_forward(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
+                                          z.data_ptr(), n, bins.width, bins.height, bins.tile_start.data_ptr(),
+                                          bins.tile_list.data_ptr(), *(m.data_ptr() for m in maps), _stream(dev)),
+            "gcp_blend_distort_forward",
+        )
+    return tuple(maps)
+
+
+def blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth, t_ckpt, a_n, b_n, grad_dist):
+    """Backward of `blend_distort_forward` for the loss <dist, grad_dist> (gcp_blend_distort_backward) -> (grad_mean [N,2],
+    grad_variance_inverse [N,2,2], grad_opacity [N,1], grad_depth [N]).  With G = grad_dist and the inclusive suffix sums
+    SA_k = sum_{j>=k} w_j, SB_k = sum_{j>=k} w_j z_j it runs the blend backward's own recursion on
+        c_k = 2 G [z_k (A_n - 2 SA_k) - (B_n - 2 SB_k)],    dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+    which is linear in c: the results ADD to those of `blend_backward_depth`.  `t_ckpt`: the checkpoints
+    `blend_forward_depth(..., with_checkpoints=True)` (or `blend_forward`) returned for the same bins and inputs; `a_n`, `b_n`:
+    what the distortion forward returned.  No atomics: two calls give the same bits."""
+    start, end, mean_f, vinv, op = _params(startpoint, endpoint, mean, variance_inverse, opacity)
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    z, _ = _depth_args(depth, None, n, dev)
+    shape = (bins.height + 1, bins.width + 1)
+    maps = []
+    for t, name in zip((a_n, b_n, grad_dist), ("a_n", "b_n", "grad_dist")):
+        t = _dev_tensor(t, name, torch.float32)
+        _require(tuple(t.shape) == shape and t.device == dev, f"{name}: expected shape {shape} on {dev}")
+        maps.append(t)
+    lib = _lib.load()
+    ck = _dev_tensor(t_ckpt, "t_ckpt", torch.float32)
+    _require(ck.numel() >= _checkpoint_floats(lib, bins),
+             "t_ckpt: too small for these bins (pass what blend_forward_depth(..., with_checkpoints=True) returned)")
+    grads = [torch.empty(n, *tail, dtype=torch.float32, device=dev) for tail in ((2,), (2, 2), (1,), ())]  # mean, vinv, opacity, depth
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_blend_distort_backward_workspace_bytes(bins.tile_capacity), dtype=torch.uint8, device=dev)
+        _lib.check(
+            lib.gcp_blend_distort_backward(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
+                                           z.data_ptr(), n, bins.width, bins.height, bins.tile_off.data_ptr(), bins.tile_capacity,
+                                           bins.tile_start.data_ptr(), bins.tile_list.data_ptr(), ck.data_ptr(),
+                                           *(m.data_ptr() for m in maps), *(g.data_ptr() for g in grads), ws.data_ptr(), ws.numel(),
+                                           _stream(dev)),
+            "gcp_blend_distort_backward",
+        )
+    return tuple(grads)
 
 
 def exclusive_scan_i32(x):
