@@ -864,11 +864,16 @@ int gcp_blend_absgrad_depth(const int32_t* start_xy, const int32_t* end_xy, cons
  *   dist(p) = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})      ( = sum_{i>j} 2 w_i w_j (z_i - z_j) )
  * — the order-based form: it equals sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list order, as the camera
  * depth the list is sorted by is (ties contribute 0).  Like the depth map it is not divided by alpha and is in units of z.
- * The forward writes three maps of (H+1)(W+1) floats: dist, a_n = A_n and b_n = B_n (a_n is NOT the alpha map: behind an
- * exactly opaque layer alpha = 1 while A_n is the sum in front of the dropped pair).  n_gauss == 0: the maps are zeroed.
+ * In float32 neither kernel forms z_k A - B (a difference of numbers of size z A whose value has size dz A: a surface 1e-2
+ * thick at depth 20 lost three digits): both carry s(z) = sum_j w_j |z - z_j| along the pixel's own contributing pairs by
+ * differences of NEIGHBOURING depths, so every term is of the size of the spread of the pixel's own layers, whatever the offset.
+ * The forward writes three maps of (H+1)(W+1) floats: dist, a_n = A_n and b_n = sum_j w_j (z_L - z_j), L the pixel's last
+ * contributing pair — NOT B_n = sum w z: opaque state for the backward of the same bins and depths (a_n is NOT the alpha map:
+ * behind an exactly opaque layer alpha = 1 while A_n is the sum in front of the dropped pair).  n_gauss == 0: the maps are zeroed.
  * The backward takes them back with t_ckpt of a checkpointed blend forward ON THE SAME BINS and G = grad_dist = dL/d dist;
- * with the inclusive suffix sums SA_k, SB_k of w and w z it runs the blend backward's own recursion on
- *   c_k = 2 G [ z_k (A_n - 2 SA_k) - (B_n - 2 SB_k) ],   dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+ * with the inclusive suffix sum SA_k = sum_{j>=k} w_j it runs the blend backward's own recursion on
+ *   c_k = 2 G s_k,  s_k = sum_j w_j |z_k - z_j|,   dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+ * s carried back to front as s_k = s_k' + (z_k' - z_k)(2 SA_k' - A_n) from s_L = b_n, k' the contributing pair behind k
  * (R = 0 behind the list, R_{k-1} = R_k + a_k (c_k - R_k), dL/do_k = T_k g_k (c_k - R_k), common = T_k a_k (c_k - R_k)) and
  * WRITES grad_mean [N,2], grad_vinv [N,4], grad_opacity [N], grad_depth [N]: the recursion is linear in c, so these add to
  * the gradients of gcp_blend_backward_depth.  0 for an empty box and for a Gaussian the binning did not list.

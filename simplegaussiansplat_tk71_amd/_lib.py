@@ -150,7 +150,7 @@ SIGNATURES = {
     "gcp_blend_absgrad_workspace_bytes": (_sz, [_i64]),
     "gcp_blend_absgrad": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 6 + [_sz, _c_void_p]),
     "gcp_blend_absgrad_depth": (ctypes.c_int, [_c_void_p] * 8 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 8 + [_sz, _c_void_p]),
-    # depth distortion (gcp_distort.hip): forward -> dist, A_n, B_n maps; backward: those, t_ckpt and grad_dist -> four gradients
+    # depth distortion (gcp_distort.hip): forward -> dist, A_n, sum w (z_L - z) maps; backward: those, t_ckpt and grad_dist -> four gradients
     "gcp_blend_distort_forward": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32] + [_c_void_p] * 6),
     "gcp_blend_distort_backward_workspace_bytes": (_sz, [_i64]),
     "gcp_blend_distort_backward": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 11 + [_sz, _c_void_p]),

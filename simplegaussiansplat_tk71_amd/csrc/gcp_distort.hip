@@ -8,20 +8,38 @@
 //     dist(p) = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})        ( = sum_{i>j} 2 w_i w_j (z_i - z_j) )
 //   the order-based form: equal to sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list order, as the camera
 //   depth is (the list is sorted by it; ties contribute 0).  Not divided by alpha, in units of z, like the depth map.
-//   Backward, G = dL/d dist(p), SA_k = sum_{j>=k} w_j, SB_k = sum_{j>=k} w_j z_j (inclusive suffix sums):
-//     c_k = 2 G [ z_k (A_n - 2 SA_k) - (B_n - 2 SB_k) ]  (= G d dist / d w_k),    dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+//   Backward, G = dL/d dist(p), SA_k = sum_{j>=k} w_j (inclusive suffix sum), s_k = sum_j w_j |z_k - z_j|:
+//     c_k = 2 G s_k  (= G d dist / d w_k),    dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
 //   and the rest is the blend backward's own recursion with this c_k (walk_back, gcp_blend_shared.hpp): R = 0 behind the list,
 //   R_{k-1} = R_k + a_k (c_k - R_k), dL/do_k = T_k g_k (c_k - R_k), common = T_k a_k (c_k - R_k).  It is linear in c: these
 //   gradients ADD to those of the image, depth and alpha maps.
-//   A_n is not the alpha map (behind an exactly opaque layer alpha = 1, A_n is the sum in front of the dropped pair), and B_n is
-//   not promised to be the depth map's bits: the forward leaves both per pixel for the backward.
+//   A_n is not the alpha map (behind an exactly opaque layer alpha = 1, A_n is the sum in front of the dropped pair).
+//   In float32 neither kernel forms these expressions as written: z_k A - B is a difference of two numbers of size z A whose
+//   value has size dz A, and a surface 1e-2 thick at depth 20 — where the regulariser works — lost three digits with them
+//   (profiles/r23_blend_rows.md).  A reference depth per tile does not cure it: z - z_ref is itself rounded when z_ref is far,
+//   and a pixel's own layers can lie much closer together than the tile's.  Both kernels therefore carry
+//     s(z) = sum_j w_j |z - z_j|   along the pixel's own contributing pairs by DIFFERENCES OF NEIGHBOURING DEPTHS only:
+//   forward   D_k = sum_{j<k} w_j (z_k - z_j) = D_k' + (z_k - z_k') A_{k-1}, k' the pixel's contributing pair in front of k: for
+//             depths in list order a sum of terms of one sign;  dist = 2 sum_k w_k D_k.  It leaves A_n and, as b_n, D_L of the
+//             pixel's LAST contributing pair L (= s(z_L): nothing lies behind L).
+//   backward  from s_L = b_n, walking back: s_k = s_k' + (z_k' - z_k) (2 SA_k' - A_n), k' the contributing pair behind k and
+//             SA_k' the inclusive suffix sum of w (s is piecewise linear in z with slope A_front - A_behind);
+//             c_k = 2 G s_k,  dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k).
+//   Forward and backward each decide which pair is the pixel's last contributing one, by w != 0 on weights that are not the
+//   same bits (T from the product / from the quotient or slow branch, another association of the exponent).  Where they
+//   disagree, s is off by the SAME (z_k - z_L) A_n on every entry of that pixel.  A constant added to every c_j leaves
+//   c_k - R_k = (c_k - sum of the convex weights behind k) unchanged but for the weight T_N-behind-L / T_{k+1} of the empty
+//   suffix: harmless wherever the weight vanished because T underflowed (that factor is then ~0).  It would cost accuracy
+//   only where a weight underflows at a T_N that is not negligible, i.e. g ~ 1e-38 inside a box that is otherwise visible.
+//   Everything is in units of the spread of the pixel's own layers, whatever the offset.  b_n is per-pixel state for the
+//   backward of the same bins and depths, not sum w z.
 //
 //   k_distort_fwd     one 256-thread block per 16x16 tile, one pixel per lane, the list front to back as k_contrib_tile walks it
 //                     (256 entries staged at a time, the per-wave hit words, the wave-uniform exit behind an exact zero, the
 //                     forward blend's association and contraction: w is the weight the image was painted with), the record
-//                     with z instead of colour.  Writes dist, A_n, B_n; no checkpoints (the backward takes those of the render's
+//                     with z instead of colour.  Writes dist, A_n, b_n = D_L; no checkpoints (the backward takes those of the render's
 //                     own forward on the same bins).
-//   k_distort_bwd     on walk_pixel / walk_back; c_k comes from the lane's SA, SB, A_n, B_n, G through walk_back's hook.  Per
+//   k_distort_bwd     on walk_pixel / walk_back; c_k comes from the lane's s, SA, A_n, G through walk_back's hook.  Per
 //                     entry five 16-lane row sums (T g d, z term, w d, w d dx, w d dx dx) by the blend's transposed butterfly cut
 //                     to five values (12 VALU), into LDS; one thread per entry folds the 16 rows into the entry's Gaussian-major
 //                     slot of 7 floats.
@@ -53,7 +71,8 @@ __global__ __launch_bounds__(256) void k_distort_fwd(const BlendArgs a, const fl
   const float fx = (float)px, fy = (float)py;
   const unsigned lane_bits = (1u << (lane & 15)) | (1u << (16 + w * 4 + (lane >> 4)));
   const int first = a.tile_start[tile], last = a.tile_start[tile + 1];
-  float T = 1.0f, A = 0.0f, B = 0.0f, acc = 0.0f;
+  float T = 1.0f, A = 0.0f, acc = 0.0f;
+  float D = 0.0f, zp = 0.0f;  // D_k' and z_k' of the pixel's last contributing pair (zp counts for nothing while A == 0)
   for (int base = first; base < last; base += kStage) {
     const int cnt = __builtin_amdgcn_readfirstlane(min(kStage, last - base));  // scalar loop bound
     __syncthreads();
@@ -77,9 +96,12 @@ __global__ __launch_bounds__(256) void k_distort_fwd(const BlendArgs a, const fl
           const float incl = T * (1.0f - ge.z * g);  // inclusive product
           if (incl != 0.0f) {                        // dropped when exactly 0
             const float wgt = T * ge.z * g;
-            acc += wgt * (zk * A - B);               // w_k (z_k A_{k-1} - B_{k-1})
-            A += wgt;
-            B += wgt * zk;
+            if (wgt != 0.0f) {                       // (a kept pair whose weight underflowed contributes nothing and moves nothing)
+              D += (zk - zp) * A;                    // D_k = z_k A_{k-1} - B_{k-1}, by neighbouring differences
+              zp = zk;
+              acc += wgt * D;
+              A += wgt;
+            }
           }
           T = incl;
         }
@@ -90,25 +112,30 @@ __global__ __launch_bounds__(256) void k_distort_fwd(const BlendArgs a, const fl
     const i64 o = (i64)py * (a.W + 1) + px;
     dist[o] = 2.0f * acc;
     a_n[o] = A;
-    b_n[o] = B;
+    b_n[o] = D;  // D_L
   }
 }
 
-// what walk_back asks per entry: c_k from the lane's suffix sums; it keeps w_k and the z term for the body
+// what walk_back asks per entry: c_k = 2 G s_k, s carried from the pixel's last contributing pair back to front; it keeps the z
+// term for the body
 struct DistHook {
   static constexpr bool kOn = true;
-  float SA = 0.0f, SB = 0.0f;  // inclusive suffix sums of w and w z over the entries handled so far
-  float A_N = 0.0f, B_N = 0.0f, G2 = 0.0f;  // the forward's A_n, B_n and 2 dL/d dist of the pixel; 0 outside the frame
+  float SA = 0.0f;             // inclusive suffix sum of w over the entries handled so far
+  float s_ = 0.0f, zp = 0.0f;  // s and z of the contributing pair behind the entry in hand; s starts as the forward's b_n = s_L
+  float A_N = 0.0f, G2 = 0.0f; // the forward's A_n and 2 dL/d dist of the pixel; 0 outside the frame
   float zt = 0.0f;             // dL/dz_k of this pixel for the entry in hand
   template <class S>
   __device__ __forceinline__ float c(const S& s, int k, float wk) {
 #pragma clang fp contract(fast)
     const float z = s.z[k];
-    SA += wk;
-    SB += wk * z;
-    const float u = A_N - 2.0f * SA;
-    zt = G2 * wk * (u + wk);
-    return G2 * (z * u - (B_N - 2.0f * SB));
+    if (wk != 0.0f) {          // an entry without weight contributes nothing and its c_k is not used: s stays where it is
+      const float dz = (SA == 0.0f) ? 0.0f : zp - z;  // nothing behind the last contributing pair: s_L as the forward left it
+      s_ += dz * (2.0f * SA - A_N);
+      zp = z;
+      SA += wk;
+    }
+    zt = G2 * wk * (A_N - 2.0f * SA + wk);
+    return G2 * s_;
   }
 };
 
@@ -129,7 +156,7 @@ __global__ __launch_bounds__(256) void k_distort_bwd(const BlendArgs a, const fl
   if (p.px <= a.W && p.py <= a.H) {
     const i64 o = (i64)p.py * (a.W + 1) + p.px;
     hook.A_N = a_n[o];
-    hook.B_N = b_n[o];
+    hook.s_ = b_n[o];
     hook.G2 = 2.0f * grad_dist[o];
   }
   const bool b1 = lane & 2;

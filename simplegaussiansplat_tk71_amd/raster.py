@@ -385,8 +385,11 @@ def blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, op
         dist = 2 sum_k w_k (z_k A_{k-1} - B_{k-1})   ( = sum_{i>j} 2 w_i w_j (z_i - z_j) )
     the order-based form: it equals sum_{i,j} w_i w_j |z_i - z_j| whenever z is non-decreasing in list order, as the camera
     depth the list is sorted by is (ties contribute 0).  Like the depth map it is not divided by alpha and is in units of z.
-    a_n = A_n and b_n = B_n are what `blend_distort_backward` needs back: a_n is not the alpha map (behind an exactly opaque
-    layer alpha = 1, a_n is the sum in front of the dropped pair)."""
+    a_n = A_n and b_n are what `blend_distort_backward` needs back: a_n is not the alpha map (behind an exactly opaque
+    layer alpha = 1, a_n is the sum in front of the dropped pair), and b_n is not B_n but sum_j w_j (z_L - z_j), L the pixel's last
+    contributing pair: the kernels do not form z_k A - B but carry sum_j w_j |z - z_j| along the pixel's pairs by differences of
+    neighbouring depths, so that every term is of the size of the spread of the pixel's own layers and not of the depth (dist and
+    the gradients are translation invariant; tests/test_blend_rows_gpu.py holds them to that at clustered depths)."""
     start, end, mean_f, vinv, op = _params(startpoint, endpoint, mean, variance_inverse, opacity)
     dev = start.device
     n = bins.n_gauss
@@ -408,8 +411,9 @@ def blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, op
 def blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth, t_ckpt, a_n, b_n, grad_dist):
     """Backward of `blend_distort_forward` for the loss <dist, grad_dist> (gcp_blend_distort_backward) -> (grad_mean [N,2],
     grad_variance_inverse [N,2,2], grad_opacity [N,1], grad_depth [N]).  With G = grad_dist and the inclusive suffix sums
-    SA_k = sum_{j>=k} w_j, SB_k = sum_{j>=k} w_j z_j it runs the blend backward's own recursion on
-        c_k = 2 G [z_k (A_n - 2 SA_k) - (B_n - 2 SB_k)],    dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+    SA_k = sum_{j>=k} w_j it runs the blend backward's own recursion on
+        c_k = 2 G s_k,  s_k = sum_j w_j |z_k - z_j|,    dL/dz_k = 2 G w_k (A_n - 2 SA_k + w_k)
+    with s carried back to front from s_L = b_n of the pixel's last contributing pair: s_k = s_k' + (z_k' - z_k) (2 SA_k' - A_n),
     which is linear in c: the results ADD to those of `blend_backward_depth`.  `t_ckpt`: the checkpoints
     `blend_forward_depth(..., with_checkpoints=True)` (or `blend_forward`) returned for the same bins and inputs; `a_n`, `b_n`:
     what the distortion forward returned.  No atomics: two calls give the same bits."""

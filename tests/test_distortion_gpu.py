@@ -2,7 +2,8 @@
 raster.blend_distort_*, cuda_kernel.render(distortion=True), GS_model_with_param.render(distortion=True) and the training
 example, against the dense float64 oracle of tests/distortion_torch.py.  Depths are sorted ascending, as the camera depth of
 a depth-ordered list is.  Tolerances are those of the depth map (tests/test_render_depth_gpu.py): TOL * z_max on the map,
-2e-4 of its own largest magnitude on every gradient."""
+2e-4 of its own largest magnitude on every gradient.
+Per-Gaussian accuracy, each row against its own condition scale and at clustered depths: tests/test_blend_rows_gpu.py."""
 import math
 import os
 

@@ -1,5 +1,6 @@
 """Depth, alpha and background from the fused blend (cuda_kernel.render, csrc/gcp_blend.hip k_blend_fwd_depth /
-k_blend_bwd_depth) and through the model (GS_model_with_param.render) against a dense fp64 oracle written here."""
+k_blend_bwd_depth) and through the model (GS_model_with_param.render) against a dense fp64 oracle written here.
+Per-Gaussian accuracy, each row against its own condition scale: tests/test_blend_rows_gpu.py."""
 import math
 import os
 
