@@ -413,6 +413,22 @@ def test_stable_sort_keys_equals_torch_stable_sort(device, n, hi):
     assert torch.equal(got_i.cpu().long(), want_i)
 
 
+@pytest.mark.parametrize("n", [4099, 100003])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_stable_sort_keys_of_a_view_that_is_not_16_byte_aligned(device, n, k):
+    """The first pass reads the caller's keys: four at a time where they lie on 16 bytes, one at a time where they do not."""
+    from simplegaussiansplat_tk71_amd import raster
+
+    g = torch.Generator().manual_seed(n + k)
+    keys = torch.randint(0, 21_600_000 + 1, (n + k,), generator=g, dtype=torch.int32)
+    view = keys.to(device)[k:]
+    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
+    want_k, want_i = torch.sort(keys[k:], stable=True)
+    got_k, got_i = raster.stable_sort_keys(view)
+    assert torch.equal(got_k.cpu(), want_k)
+    assert torch.equal(got_i.cpu().long(), want_i)
+
+
 def test_render_cameras_on_two_streams_equals_sequential(device):
     from simplegaussiansplat_tk71_amd import raster
 

@@ -214,6 +214,24 @@ def test_sort_rects_equals_torch_stable_sort_of_the_keys(device, n, wmax, hmax):
     assert raster.rects_key_bits(rects.to(device)) == max(1, int(key.max()).bit_length())
 
 
+@pytest.mark.parametrize("n", [4099, 100003])
+def test_sort_rects_of_a_view_that_is_not_16_byte_aligned(device, n):
+    """gcp_sort_rects on rows 1.. of a rect list: 8 bytes past a 16-byte boundary, so the first pass loads rect by rect."""
+    import cuda_kernel as ck
+    from simplegaussiansplat_tk71_amd import raster
+
+    wmax, hmax = 1919, 1079
+    g = torch.Generator().manual_seed(n + 1)
+    rects = torch.stack([torch.randint(0, wmax + 1, (n + 1,), generator=g), torch.randint(0, hmax + 1, (n + 1,), generator=g)], 1).to(torch.int32)
+    view = rects.to(device)[1:]
+    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
+    key = rects[1:, 1] * 10000 + rects[1:, 0]
+    want_k, want_i = torch.sort(key, stable=True)
+    for how in (dict(key_bits=ck.pixel_key_bits(wmax, hmax)), dict(image_size=(wmax, hmax)), dict()):
+        got_k, got_i = raster.sort_rects(view, **how)
+        assert torch.equal(got_k.cpu(), want_k) and torch.equal(got_i.cpu().long(), want_i), how
+
+
 def test_sort_rects_refuses_negative_coordinates_when_it_has_to_look(device):
     from simplegaussiansplat_tk71_amd import raster
 
