@@ -183,6 +183,8 @@ __device__ __forceinline__ float wave_reduce(float v) {
 // the look-back re-reads the END of the neighbouring tile and wants it cached.  So the aligned stores are
 // non-temporal, and so are the tile loads of all waves but the last one in scan order, plus `param` in the
 // backward, which no look-back touches: neutral on the forward and cfg2 and +1.3 % on the backward.
+// (What the binary does today: no load of the forward kernels carries `nt`, and in the backward only `param`'s do —
+// the wave-uniform `nt_main` branches of scan_tile compile to plain loads.)
 template <bool ALIGNED, bool NT = false>
 __device__ __forceinline__ float4_t ld4(const float* p) {
   if (ALIGNED) {
@@ -832,16 +834,31 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
 
 }
 
-// Forward modes: six blocks per CU (<= 80 VGPRs), which the rare descriptor walk must not cost.  The cumprod backward holds
+// Forward modes: registers for six blocks per CU (<= 80 VGPRs), which the rare descriptor walk must not cost.  More does not
+// pay: seven and eight waves per SIMD (<= 64 VGPRs with a look-back batch of three) measured level to 0.5 % slower on cfg3,
+// and the plain forward scans are FASTER with fewer tiles resident, which launch_scan arranges with
+// resident_tiles_lds() below (profiles/r24_fwd_occupancy.md).  The cumprod backward holds
 // three arrays per element: four blocks per CU (<= 128 VGPRs, no scratch: tests/test_bwd_occupancy.py), so that a tile
 // waiting for its group ends leaves three others' loads in flight and not two (cfg3: 457 -> 436 us; a launch whose waves ALL
 // take the key fall-back pays 2-3 % for it: profiles/r08_bwd_occupancy.md).  The reverse sum, the indexed and the
-// in-place scans are left to the register allocator.
+// in-place scans are left to the register allocator (the reverse sum: 105-107 VGPRs, four blocks per CU, its best step).
 template <int MODE>
 constexpr int waves_per_simd(bool indexed, bool inplace, bool upper) {
   if (Mode<MODE>::kBwd) return 4;
   if (Mode<MODE>::kRev || indexed || inplace) return upper ? 8 : 1;
   return 6;
+}
+// Dynamic LDS a launch of the plain forward scans (MODE 0 / 1; not carry, indexed or in place) asks for and never
+// touches: 48 KB per block lets three blocks share a CU's 160 KB and not the six their registers allow.  On cfg3 the
+// forward takes 328 us at three resident tiles per CU against 338-342 at four, 344-347 at five and 348 at six (367 at
+// two): the kernel is limited by HBM and twelve waves per CU already keep 96 KB of loads in flight; at six the waves
+// queue behind the memory system (same wave lifetime, twice the waves).  The device code is the same whatever this
+// returns.  The price: inputs whose groups are ALL longer than a tile, where the tiles in flight are the look-ahead of
+// the chain through the descriptor tree, lose 7-15 %.  The carry form (19 % slower at three blocks: its carry[] gathers want
+// the parallelism), the reverse sum (best at the four blocks its registers give it) and the cumprod backward get none.
+template <int MODE>
+constexpr unsigned resident_tiles_lds() {
+  return Mode<MODE>::kRev ? 0u : 48u * 1024u;
 }
 template <int MODE, bool ALIGNED, bool CARRY, bool INDEXED = false, bool INPLACE = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(waves_per_simd<MODE>(INDEXED, INPLACE, false), waves_per_simd<MODE>(INDEXED, INPLACE, true))))
@@ -1316,8 +1333,8 @@ int launch_scan(const float* in0, const float* in1, const float* in2, const int*
     if (aligned) hipLaunchKernelGGL((gcp_scan_main<MODE, true, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((gcp_scan_main<MODE, false, true>), grid, block, 0, stream, a);
   } else {
-    if (aligned) hipLaunchKernelGGL((gcp_scan_main<MODE, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((gcp_scan_main<MODE, false, false>), grid, block, 0, stream, a);
+    if (aligned) hipLaunchKernelGGL((gcp_scan_main<MODE, true, false>), grid, block, resident_tiles_lds<MODE>(), stream, a);
+    else hipLaunchKernelGGL((gcp_scan_main<MODE, false, false>), grid, block, resident_tiles_lds<MODE>(), stream, a);
   }
   GCP_HIP(hipGetLastError());
   if (ntiles > 1) {
