@@ -42,18 +42,18 @@ def draw(cum, n_out, seed):
     slot bool (M,).  Counter (r, 0, 0, 2), t = (r0 T) >> 32, source = upper bound of t in cum[1:]."""
     cum = np.asarray(cum, dtype=np.int64)
     n, m, total = cum.size - 1, int(n_out), int(cum[-1])
-    r = np.arange(m, dtype=np.uint64)
     slot = np.ones(m, dtype=bool)
     slot[:n] = (cum[1:] == cum[:-1])[:m]
     if total == 0:
         src = (np.arange(m) % max(n, 1)).astype(np.int64)
         times = np.zeros(n, dtype=np.int64)
     else:
+        r = np.nonzero(slot)[0].astype(np.uint64)  # only a slot draws: the Philox words of the other rows would be thrown away
         zero = np.zeros_like(r)
         rnd = philox4x32_10(np.stack([r, zero, zero, zero + np.uint64(DRAW_DOMAIN)], axis=-1), _key(seed, r.shape))
         t = (rnd[:, 0].astype(np.uint64) * np.uint64(total)) >> np.uint64(32)
-        drawn = np.searchsorted(cum[1:], t.astype(np.int64), side="right")
-        src = np.where(slot, drawn, np.arange(m))
+        src = np.arange(m, dtype=np.int64)
+        src[slot] = np.searchsorted(cum[1:], t.astype(np.int64), side="right")
         times = np.bincount(src[slot], minlength=n).astype(np.int64)
     kind = np.ones(m, dtype=np.uint8)
     kind[:n] = ~((src[:n] == np.arange(n)) & (times == 0))
@@ -68,12 +68,13 @@ def relocated(opacity, log_scale, copies, min_opacity=MIN_OPACITY):
     n = (copies.long() + 1).clamp(max=MAX_COPIES)
     o_new = 1 - (1 - o) ** (1.0 / n.double())
     denom = torch.zeros_like(o)
-    for j in range(o.numel()):
-        acc = 0.0
-        for i in range(1, int(n[j]) + 1):
+    for count in n.unique().tolist():  # the same sum, term by term in the same order, for all rows of one n at once (n <= 51)
+        rows = n == count
+        x, acc = o_new[rows], torch.zeros(int(rows.sum()), dtype=torch.float64)
+        for i in range(1, count + 1):
             for k in range(i):
-                acc += math.comb(i - 1, k) * (-1) ** k * float(o_new[j]) ** (k + 1) / math.sqrt(k + 1)
-        denom[j] = acc
+                acc += math.comb(i - 1, k) * (-1) ** k * x ** (k + 1) / math.sqrt(k + 1)
+        denom[rows] = acc
     new_scale = log_scale.double() + torch.log(o / denom)[:, None]
     return torch.logit(o_new.clamp(min_opacity, 1 - 2.0 ** -23))[:, None], new_scale
 

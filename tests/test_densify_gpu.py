@@ -27,14 +27,15 @@ def device_plan(sc, device, n_split=2, hyper=dt.HYPER):
     lib = _lib.load()
     n = sc["norm"].numel()
     norm, views, log_scale, opacity = (sc[k].to(device).contiguous() for k in ("norm", "views", "variance_scale", "opacity"))
-    count, offset = torch.empty(n, dtype=torch.int32, device=device), torch.empty(n + 1, dtype=torch.int32, device=device)
-    action = torch.empty(n, dtype=torch.uint8, device=device)
+    # every output starts at a value the kernels never write: a word that no thread reaches shows in the comparison
+    count, offset = torch.full((n,), -1, dtype=torch.int32, device=device), torch.full((n + 1,), -1, dtype=torch.int32, device=device)
+    action = torch.full((n,), 255, dtype=torch.uint8, device=device)
     ws = torch.empty(lib.gcp_densify_plan_workspace_bytes(n), dtype=torch.uint8, device=device)
     _lib.check(lib.gcp_densify_plan(norm.data_ptr(), views.data_ptr(), log_scale.data_ptr(), opacity.data_ptr(), n, hyper["grad_threshold"],
                                     hyper["dense_extent"], hyper["prune_extent"], hyper["min_opacity"], n_split, count.data_ptr(),
                                     action.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel(), _stream(device)), "gcp_densify_plan")
     m = int(offset[n])
-    src_row, kind = torch.empty(m, dtype=torch.int32, device=device), torch.empty(m, dtype=torch.uint8, device=device)
+    src_row, kind = torch.full((m,), -1, dtype=torch.int32, device=device), torch.full((m,), 255, dtype=torch.uint8, device=device)
     _lib.check(lib.gcp_densify_fill(action.data_ptr(), offset.data_ptr(), n, m, src_row.data_ptr(), kind.data_ptr(), _stream(device)),
                "gcp_densify_fill")
     return {"count": count, "action": action, "offset": offset, "M": m, "src_row": src_row, "kind": kind}
