@@ -1,7 +1,10 @@
 """Opacity compensation of the covariance dilation on the GPU (csrc/gcp_splat.hip with GCP_SPLAT_ANTIALIAS, gs_model's
 `antialias`): opacity = sigmoid(o) rho, rho = sqrt(det Sigma / det Sigma'), against the PyTorch formulation of
-tests/test_splat_gpu.py with rho formed from the same clamped covariance and invert_2x2_batch's det + 1e-6, written out
-below; what the option must leave alone; degenerate covariances; the energy of a splat; and end to end."""
+tests/test_splat_gpu.py with rho formed from the same clamped covariance and invert_2x2_batch's det + 1e-6
+(`formulation(antialias=True)`, `compensation`); what the option must leave alone; degenerate covariances; the energy of a
+splat; and end to end.
+The per-row checks of rho and its gradient chain — the row rule against float64, sub-pixel, large and thin splats, pixel
+centres, the edge scene, position and alignment — live in tests/test_projection_rows_gpu.py."""
 import math
 
 import numpy as np
@@ -9,8 +12,8 @@ import pytest
 import torch
 
 from oracle import dense_render as dr
-from oracle import gs_forward_torch as gft
 from simplegaussiansplat_tk71_amd import gs_model as gm
+from tests import test_projection_rows_gpu as row_checks
 from tests.test_sh3_gpu import NAMES, SHAPES, TILE_LOGIT, random_world, torch_sh
 from tests.test_splat_gpu import formulation, small_model, world
 from tests.util import assert_parity
@@ -25,38 +28,13 @@ OUTPUTS = ("variance_inverse", "opacity", "l_d", "mean")
 IDS = dict(ids=lambda s: "x".join(map(str, s)))
 
 
-def rho_torch(mean, variance_q, variance_scale, P, K, cov_eps):
-    """rho (C, N) of every Gaussian in every camera, by the operations of `formulation` up to the pixel covariance:
-    det0 on the clamped covariance before cov_eps, det = invert_2x2_batch's a d - b c + 1e-6 on the dilated one;
-    rho = sqrt(max(det0, 0) / det), 0 (and no gradient) where det0 <= 0."""
-    dev, dt = mean.device, mean.dtype
-    fmax = torch.finfo(torch.float32).max
-    homo = torch.hstack((mean, torch.ones((mean.shape[0], 1), device=dev, dtype=dt)))[None]
-    mean_camera = homo @ P.transpose(1, 2)
-    q = variance_q / torch.norm(variance_q, dim=1, keepdim=True).clamp_min(1e-8)
-    rot = gft.qvec_to_rotmat_batch(q)
-    s_diag = torch.eye(3, dtype=dt, device=dev)[None] * torch.exp(variance_scale)[:, None, :]
-    cov = rot @ s_diag @ s_diag.transpose(1, 2) @ rot.transpose(1, 2)
-    cov_cam = P[:, None, :, 0:3] @ cov[None] @ P.transpose(1, 2)[:, None, 0:3, :]
-    J = gft.pixel_jacobian_batch(K, mean_camera)
-    raw = (J @ cov_cam @ J.transpose(2, 3)).clamp(max=fmax / 1000, min=-fmax / 1000)
-    det0 = raw[..., 0, 0] * raw[..., 1, 1] - raw[..., 0, 1] * raw[..., 1, 0]
-    full = raw + cov_eps * torch.eye(2, dtype=dt, device=dev)[None, None]
-    det = full[..., 0, 0] * full[..., 1, 1] - full[..., 0, 1] * full[..., 1, 0] + 1e-6
-    positive = det0 > 0
-    return torch.where(positive, torch.sqrt(torch.where(positive, det0, torch.ones_like(det0)) / det), torch.zeros_like(det0)), det0
-
-
 def antialiased_formulation(leaves, w, degree, frame, options, fixed, dtype):
-    """tests/test_splat_gpu.formulation in `dtype` on the lists `fixed`, its "opacity" multiplied by rho.
+    """tests/test_splat_gpu.formulation(antialias=True) in `dtype` on the lists `fixed`: its "opacity" is sigmoid(o) rho.
     -> (cams, rho (C, N), det0 (C, N))"""
     P, K = w["P"].to(dtype), w["K"].to(dtype)
     cams, _ = formulation(*(leaves[k] for k in NAMES), P, K, w["wh"], TILE_LOGIT, degree, torch_sh(frame, P), cov_eps=options["cov_dilation"],
-                          clamp_colour=options.get("clamp_colour", False), fixed=fixed)
-    rho, det0 = rho_torch(leaves["mean"], leaves["variance_q"], leaves["variance_scale"], P, K, options["cov_dilation"])
-    for c, cam in enumerate(cams):
-        cam["opacity"] = cam["opacity"] * rho[c, cam["index"]][:, None]
-    return cams, rho, det0
+                          clamp_colour=options.get("clamp_colour", False), fixed=fixed, antialias=True)
+    return cams, torch.stack([cam["rho_all"] for cam in cams]), torch.stack([cam["det0_all"] for cam in cams])
 
 
 def upstream_loss(cams, n, upstream, seed=1):
@@ -225,7 +203,9 @@ def test_degenerate_covariances(device):
     """Row A (det0 = 0) has "opacity" exactly 0; B and C, whose det0 is at most what rounding leaves of a rank-1 matrix
     (|det0| <= a few 2^-24 a d ~ 1e-5 here, det >= 0.3 d ~ 1.2: rho <= 3e-3), have an opacity below 1e-2 sigmoid(o), and
     wherever an opacity is exactly 0 the logit's gradient is exactly 0.  Every output and every gradient of every row is
-    finite, and the ordinary rows — outputs and gradients — are bit-equal to the scene without the three."""
+    finite, and the ordinary rows — outputs and gradients — are bit-equal to the scene without the three.
+    With "opacity" alone upstream the three are also held one by one: the logit identity, an exactly zero gradient row in every
+    parameter where rho is exactly 0, and the rank-deficient row's bound on rho (the comment in the body)."""
     w, both, at, ordinary = _degenerate_scene(device)
     n = len(ordinary)
     opts = dict(L_max=2, centres="subpixel", cov_dilation=DILATION, antialias=True, with_depth=True)
@@ -233,13 +213,13 @@ def test_degenerate_covariances(device):
     ups = {k: torch.randn((n + 3, *shape), generator=gen).to(device) for k, shape in
            (("variance_inverse", (2, 2)), ("opacity", (1,)), ("l_d", (3,)), ("mean", (2,)), ("depth", ()))}
 
-    def run(params, ids):
+    def run(params, ids, upstream=tuple(ups)):
         """ids: the combined scene's row of every Gaussian of `params` -> per-Gaussian outputs and gradients"""
         leaves = [params[k].clone().requires_grad_(True) for k in NAMES]
         cams, grad_iter, _ = gm.camera_inputs(*leaves, w["P"], w["K"], w["wh"], TILE_LOGIT, **opts)
         cam = cams[0]
         ids = torch.tensor(ids, device=device)
-        sum(((cam[k] * ups[k][ids[cam["index"]]]).sum() for k in ups)).backward()
+        sum(((cam[k] * ups[k][ids[cam["index"]]]).sum() for k in upstream)).backward()
         cam = {k: v.detach() for k, v in cam.items()}
         rows = torch.full((len(ids),), -1, dtype=torch.long, device=device)
         rows[cam["index"]] = torch.arange(cam["index"].numel(), device=device)
@@ -259,6 +239,33 @@ def test_degenerate_covariances(device):
     assert bool((alpha >= 0).all()) and bool((alpha <= 1e-2 * 0.5).all())
     zero = cam["opacity"][:, 0] == 0
     assert float(grads[3][cam["index"][zero]].abs().max()) == 0.0
+    # the three rows one by one, with "opacity" alone upstream (tests/test_projection_rows_gpu.py's conditions on a row whose
+    # det0 is round-off).  Rank-deficient by that file's definition, det0 <= 2^-20 a0 d0 in float64 on the float32 parameters,
+    # is C alone: A and B are diagonal covariances, whose det0 = a0 d0 is exact in any precision that holds it (float64:
+    # rho = 1e-40 and 3.9e-21; in float32 A underflows to 0 and B's a0 is a denormal of three bits).  So the bound
+    # rho <= sqrt(2^-20 a0 d0 / det) is C's; all three are held to rho >= 0, the logit identity at 4 x the float32
+    # formulation's own figure on this scene, finite gradients, and an exactly zero gradient row in every parameter where
+    # the kernel's rho is exactly 0 (A, by the assertion above; on the MI355X also C: profiles/r26_antialias_rows.md).
+    cam_o, _, _, grads_o = run(both, list(range(n + 3)), upstream=("opacity",))
+    host = {k: both[k].cpu() for k in NAMES}
+    host.update(P=w["P"].cpu(), K=w["K"].cpu(), wh=w["wh"].cpu())
+    cfg = ("splat", {"centres": "subpixel", "cov_dilation": DILATION, "antialias": True}, 2, 9, "camera", True)
+    fixed = row_checks.lists_of([cam_o])
+    _, c64 = row_checks.run_formulation(host, cfg, torch.float64, fixed)
+    l32, c32 = row_checks.run_formulation(host, cfg, torch.float32, fixed)
+    up = ups["opacity"].cpu()[None]
+    f32 = row_checks.path_gradients(l32, c32, {"opacity": up}, ("opacity",))["opacity"]
+    got = {k: (torch.zeros_like(both[k]) if g is None else g).detach().cpu().double().reshape(n + 3, -1) for k, g in zip(NAMES, grads_o)}
+    deficient = row_checks.rank_deficient(c64)
+    print("rank-deficient rows of the scene:", sorted(deficient), "| A, B, C are", at, "| float64 rho of the three", c64[0]["rho_all"][list(at)].tolist())
+    assert deficient == {at[2]}
+    failures = []
+    row_checks.check_logit_identity("degenerate scene", host, [cam_o], got["opacity"], c32, f32["opacity"], up, failures)
+    dark = row_checks.check_nothing_passes_a_zero("degenerate scene", n + 3, [cam_o], got, failures)
+    row_checks.check_rank_deficient_rows("degenerate scene", [at[2]], [cam_o], c64, host["opacity"], failures)
+    print("rows whose rho is exactly 0:", dark.nonzero().flatten().tolist())
+    assert bool(dark[at[0]]) and all(bool(torch.isfinite(got[k][list(at)]).all()) for k in NAMES)
+    assert not failures, "\n".join(failures)
     # the ordinary rows do not notice their neighbours
     o = torch.tensor(ordinary, device=device)
     assert torch.equal(kept[o], kept_ref)

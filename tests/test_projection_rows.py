@@ -6,9 +6,9 @@ import pytest
 import torch
 
 from oracle import gs_forward_torch as gft
-from tests.test_projection_rows_gpu import (BIG, CLAMP_LOG_SCALE, CONFIGS, EDGE_CONFIGS, EDGE_CULLED, EDGE_ROWS, MARGIN, NAMES, RTOL, SHAPES, SIZES,
-                                            check_case, edge_scene, lists_of, path_gradients, paths_of, position_config, row_norm,
-                                            run_formulation, shape_id, sub_world, upstreams, world)
+from tests.test_projection_rows_gpu import (BIG, CASES, CLAMP_LOG_SCALE, CONFIGS, EDGE_CONFIGS, EDGE_CULLED, EDGE_RANK_DEFICIENT, EDGE_ROWS, MARGIN,
+                                            NAMES, ROW_CASES, RTOL, SHAPES, SIZES, row_case_id, check_case, edge_scene, lists_of, path_gradients, paths_of,
+                                            position_config, row_norm, run_formulation, shape_id, sub_world, upstreams, world)
 
 
 def own_lists_run(w, cfg):
@@ -18,16 +18,32 @@ def own_lists_run(w, cfg):
     return run_formulation(w, cfg, torch.float32, lists_of(cams))
 
 
-@pytest.mark.parametrize("config", CONFIGS)
-@pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
-def test_float32_formulation_stays_under_the_cap(shape, config, capsys):
+@pytest.mark.parametrize("shape,case", ROW_CASES, ids=row_case_id)
+def test_float32_formulation_stays_under_the_cap(shape, case, capsys):
+    """Every (configuration, kind of world, shape) of the GPU file.  Under antialias also: det0 > 0 in float32 and in float64
+    on every kept row (no row of a world is rank-deficient: `check_case`), and rho is where the kind is meant to put it: a
+    median below 0.05 on the subpixel worlds, above 0.9 on the large ones.  Prints rho min / median / max per camera."""
+    config, kind = CASES[case]
     cfg = CONFIGS[config]
-    w = world(shape, cfg[3])
+    w = world(shape, cfg[3], kind)
     failures = []
-    got, want, _ = check_case(f"{shape_id(shape)} {config}", w, cfg, own_lists_run(w, cfg), failures, median=False, who="(float32 again)")
+    leaves, cams = own_lists_run(w, cfg)
+    got, want, _ = check_case(f"{shape_id(shape)} {case}", w, cfg, (leaves, cams), failures, median=False, who="(float32 again)")
     assert not failures, "\n".join(failures)
     for path in paths_of(cfg):
         assert all(torch.isfinite(g[path][k]).all() for g in (got, want) for k in NAMES)
+    if cfg[1].get("antialias"):
+        _, c64 = run_formulation(w, cfg, torch.float64, lists_of(cams))
+        for c, (a, b) in enumerate(zip(cams, c64)):
+            index = a["index"]
+            assert bool((a["det0_all"][index] > 0).all()) and bool((b["det0_all"][index] > 0).all())
+            rho = b["rho_all"].detach()[index]
+            print(f"RHO {shape_id(shape)} {case} camera {c}: kept {index.numel()} | rho min {float(rho.min()):.2e} median {float(rho.median()):.2e} "
+                  f"max {float(rho.max()):.2e}")
+            if kind == "subpixel":
+                assert float(rho.median()) < 0.05
+            if kind == "large":
+                assert float(rho.median()) > 0.9
 
 
 @pytest.mark.parametrize("family", EDGE_CONFIGS)
@@ -45,11 +61,32 @@ def test_edge_scene_keeps_and_culls_what_it_is_meant_to(family):
     assert float((z[0] + z[1]) + z[2] + P[2, 3]) == 0.0
     assert float((w["mean"].double() @ P[2, :3].double() + P[2, 3].double())[row["depth 0"]]) <= 0.0
     failures = []
-    got, want, f32 = check_case(f"edge {family}", w, cfg, (leaves, cams), failures, median=False, who="(float32 again)", cap=False)
+    antialias = cfg[1].get("antialias", False)
+    got, want, f32 = check_case(f"edge {family}", w, cfg, (leaves, cams), failures, median=False, who="(float32 again)", cap=False,
+                                deficient=[row[k] for k in EDGE_RANK_DEFICIENT] if antialias else ())
     assert not failures, "\n".join(failures)
+    if antialias:  # what EDGE_RANK_DEFICIENT's comment says of the two rows float32 cannot follow float64 on
+        _, c64 = run_formulation(w, cfg, torch.float64, lists_of(cams))
+        a, b = cams[0], c64[0]
+        i, j = row["covariance clamp"], row["needle"]
+        print("edge", family, "covariance clamp: float64 det0, det", float(b["det0_all"][i]), float(b["det_all"][i]), "| float32 rho", float(a["rho_all"][i]),
+              "| needle: float64 det0 / (a0 d0)", float(b["det0_all"][j] / (b["cov0_all"][j, 0, 0] * b["cov0_all"][j, 1, 1])), "rho", float(b["rho_all"][j]),
+              "| float32 d0, det0, rho", float(a["cov0_all"][j, 1, 1]), float(a["det0_all"][j]), float(a["rho_all"][j]))
+        assert float(b["det0_all"][i]) < 0 and float(b["det_all"][i]) < 0 and float(b["rho_all"][i]) == 0.0
+        a0 = float(a["cov0_all"][i, 0, 0])
+        assert abs(float(a["cov0_all"][i, 0, 1])) < 1e-2 and float(a["rho_all"][i]) == pytest.approx((a0 / (a0 + 0.3)) ** 0.5, rel=1e-6)
+        assert float(b["det0_all"][j]) > 0.5 * float(b["cov0_all"][j, 0, 0] * b["cov0_all"][j, 1, 1]) and 1e-6 < float(b["rho_all"][j]) < 1e-5
+        assert 0.0 <= float(a["rho_all"][j]) <= 5 * float(b["rho_all"][j])  # the row rule's reach with the float32 formulation at 0
+        for cam in (a, b):
+            assert torch.isfinite(cam["rho_all"][cam["index"]]).all()
     for path in got:
         for k in NAMES:
-            assert torch.isfinite(want[path][k]).all() and torch.isfinite(f32[path][k]).all(), (path, k)
+            assert torch.isfinite(f32[path][k]).all(), (path, k)
+            if antialias and path == "opacity":  # EDGE_RANK_DEFICIENT: float64 has det < 0 there and no gradient of rho
+                assert bool(torch.isnan(want[path][k][i]).any()) == (k in ("mean", "variance_q", "variance_scale")), k
+                assert torch.isfinite(want[path][k][:i]).all(), k
+            else:
+                assert torch.isfinite(want[path][k]).all(), (path, k)
             for name in EDGE_CULLED:
                 assert float(want[path][k][row[name]].abs().max()) == 0.0
         for side in (want, f32):
@@ -87,6 +124,39 @@ def test_row_rule_resolves_one_wrong_degree_3_constant(monkeypatch):
     print("rows", int(live.sum()), "outside the row rule", int(outside.sum()), "median row-relative change", float(change.median()),
           "| rows whose change exceeds the per-tensor bound", int(((a - b).abs().amax(dim=1) > old_bound).sum()), "bound", old_bound)
     assert int(outside.sum()) > 0.5 * int(live.sum())
+
+
+def test_row_rule_resolves_a_compensation_a_tenth_of_a_percent_off(monkeypatch):
+    """The resolution of the row rule on the rho chain.  The float64 formulation with rho (1 + 1e-3 rho) in the place of rho
+    stands in for a kernel whose compensation is a tenth of a percent off on the larger splats, on the ordinary 1291 world:
+    more than half of the live rows of opacity -> mean, -> variance_q and -> variance_scale fall outside the rule.  Printed
+    beside each: how many rows the per-tensor bound of tests/test_antialias_gpu.py (5e-4 of the largest entry of the float64
+    gradient with "opacity" alone upstream) would have noticed."""
+    import tests.test_splat_gpu as splat
+
+    cfg = CONFIGS["splat-all-antialias-deg3of16-world-depth"]
+    w = world(SHAPES[1], 16)
+    fixed = lists_of(own_lists_run(w, cfg)[1])
+    ups = upstreams(w, cfg)
+    want = path_gradients(*run_formulation(w, cfg, torch.float64, fixed), ups, ("opacity",))["opacity"]
+    f32 = path_gradients(*run_formulation(w, cfg, torch.float32, fixed), ups, ("opacity",))["opacity"]
+    exact = splat.compensation
+
+    def off(cov0, cov_pix):
+        rho, det0, det = exact(cov0, cov_pix)
+        return rho * (1 + 1e-3 * rho), det0, det
+
+    monkeypatch.setattr(splat, "compensation", off)
+    got = path_gradients(*run_formulation(w, cfg, torch.float64, fixed), ups, ("opacity",))["opacity"]
+    for k in ("mean", "variance_q", "variance_scale"):
+        a, b, c = got[k], want[k], f32[k]
+        live = row_norm(b) > 0
+        outside = ~(row_norm(a - b) <= RTOL * row_norm(b) + MARGIN * row_norm(c - b))
+        old_bound = 5e-4 * float(b.abs().max())
+        print("opacity ->", k, "rows", int(live.sum()), "outside the row rule", int(outside.sum()), "median row-relative change",
+              float((row_norm(a - b) / row_norm(b))[live].median()), "| rows whose change exceeds the per-tensor bound",
+              int(((a - b).abs().amax(dim=1) > old_bound).sum()), "bound", old_bound)
+        assert int(live.sum()) > 1000 and int(outside.sum()) > 0.5 * int(live.sum()), k
 
 
 def test_position_worlds_keep_something_and_cull_something():

@@ -21,7 +21,7 @@ ILIM = torch.iinfo(torch.int32).max / 1000
 
 
 def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile_max_width, L_max, sh, cov_eps=1e-6, clamp_colour=False,
-                fixed=None, centres="subpixel"):
+                fixed=None, centres="subpixel", antialias=False):
     """oracle/gs_forward_torch.camera_inputs (its helpers, its order of operations, any float dtype) with three changes:
       * the centre stays a float, c = clamp(mean_pixel) + 0.5, and the box goes around it: with h = min(3-sigma half extent,
         box clamp), columns ceil(cx - h) .. floor(cx + h), rows likewise; kept: depth > 0, box not empty, x0 < W, x1 > 0,
@@ -34,7 +34,10 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
     centres: "subpixel" as above; "pixel": the kernels of csrc/gcp_splat.hip asked for integer centres (c = clamp(mean_pixel),
     no 0.5, the box rule above around it; the caller truncates "mean"); "project": csrc/gcp_project.hip, the rule of
     oracle/gs_forward_torch.camera_inputs (m = trunc(c), b = trunc(min(half, box clamp)), box m - b .. m + b, kept: depth > 0,
-    b_x != 0, m_x - b_x < W, m_x + b_x > 0, m_y - b_y < H, m_y + b_y > 0), "mean" again the float c."""
+    b_x != 0, m_x - b_x < W, m_x + b_x > 0, m_y - b_y < H, m_y + b_y > 0), "mean" again the float c.
+    antialias: "opacity" is sigmoid(o) rho, rho = `compensation` of the same pixel covariance; every cam then also holds, for
+    ALL Gaussians in their own order, "rho_all" (N,), "det0_all" (N,), "det_all" (N,) and "cov0_all" (N, 2, 2), the clamped
+    covariance before `cov_eps`."""
     if centres not in ("subpixel", "pixel", "project"):
         raise ValueError(centres)
     dev, dt = mean.device, mean.dtype
@@ -53,7 +56,8 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
     cov = rot @ s_diag @ s_diag.transpose(1, 2) @ rot.transpose(1, 2)
     cov_cam = P[:, None, :, 0:3] @ cov[None] @ P.transpose(1, 2)[:, None, 0:3, :]
     J = gft.pixel_jacobian_batch(K, mean_camera)
-    cov_pix = (J @ cov_cam @ J.transpose(2, 3)).clamp(max=fmax / 1000, min=-fmax / 1000) + cov_eps * torch.eye(2, dtype=dt, device=dev)[None, None]
+    cov0 = (J @ cov_cam @ J.transpose(2, 3)).clamp(max=fmax / 1000, min=-fmax / 1000)
+    cov_pix = cov0 + cov_eps * torch.eye(2, dtype=dt, device=dev)[None, None]
     half = gft.box_halfsize(cov_pix.detach())
     view = -mean_camera / torch.norm(mean_camera, dim=-1, keepdim=True).clamp_min(1e-8)
     l_d = sh(L_max, color[None].expand(n_cam, -1, -1, -1).transpose(2, 3), view)
@@ -61,6 +65,8 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
         l_d = l_d.clamp(min=0)
     vinv = gft.invert_2x2_batch(cov_pix)
     alpha = torch.sigmoid(opacity)
+    if antialias:
+        rho, det0, det = compensation(cov0, cov_pix)
 
     h = half.clamp(max=gft.box_clamp(torch.tensor([[width, height]]), tile_max_width, dev))
     lo = torch.ceil((centre.detach() - h).clamp(min=-ILIM, max=ILIM)).to(torch.int32)
@@ -86,7 +92,21 @@ def formulation(mean, variance_q, variance_scale, opacity, color, P, K, wh, tile
         cams.append({"boxsize": torch.prod((end - start + 1).long(), dim=1), "startpoint": start, "endpoint": end,
                      "mean": centre[c, index], "variance_inverse": vinv[c, index], "opacity": alpha[index], "l_d": l_d[c, index],
                      "index": index, "depth": mean_camera[c, index, 2], "centre_all": centre[c]})
+        if antialias:
+            cams[-1]["opacity"] = alpha[index] * rho[c, index][:, None]
+            cams[-1].update(rho_all=rho[c], det0_all=det0[c], det_all=det[c], cov0_all=cov0[c])
     return cams, grad_iter
+
+
+def compensation(cov0, cov_pix):
+    """The opacity compensation of the covariance dilation, (rho, det0, det) of (..., 2, 2) covariances: det0 = a0 d0 - b c on
+    the clamped entries before cov_eps, det = invert_2x2_batch's a d - b c + 1e-6 on the dilated ones,
+    rho = sqrt(det0 / det) where det0 > 0, and 0 with no gradient elsewhere."""
+    det0 = cov0[..., 0, 0] * cov0[..., 1, 1] - cov0[..., 0, 1] * cov0[..., 1, 0]
+    det = cov_pix[..., 0, 0] * cov_pix[..., 1, 1] - cov_pix[..., 0, 1] * cov_pix[..., 1, 0] + 1e-6
+    positive = det0 > 0
+    rho = torch.where(positive, torch.sqrt(torch.where(positive, det0, torch.ones_like(det0)) / det), torch.zeros_like(det0))
+    return rho, det0, det
 
 
 _WORLDS = {}
