@@ -18,6 +18,10 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --centres subpixel --dilation 0.3 --antialias
                                                              # the same dilation with its opacity compensation: a Gaussian
                                                              # keeps the energy it had before the dilation (Mip-Splatting's 2-D filter)
+    python examples/train_cameras.py --filter-3d --centres subpixel --dilation 0.1 --antialias
+                                                             # full Mip-Splatting: the 3-D smoothing filter (a per-Gaussian low-pass
+                                                             # from the training cameras' sampling rates, recomputed every
+                                                             # --filter-every iterations) with the 2-D filter above
     python examples/train_cameras.py --centres subpixel --densify device --densify-on screen
                                                              # split / clone / prune in one pass of HIP kernels that keeps Adam's
                                                              # moments, decided on the screen-space gradient of the centres
@@ -103,7 +107,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
-          screen_grad="signed", distortion_reg=0.0, distortion_from=0):
+          screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -147,6 +151,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     black where no `background` is set) and the loss gains L * mean(distortion map) — the depth distortion loss of Mip-NeRF 360 /
     2DGS (`cuda_kernel.render`), in units of camera-space depth; the weight is not tuned here.  With L = 0 (the default) no
     step changes.
+    `filter_3d`: Mip-Splatting's 3-D smoothing filter (GS_model_with_param(filter_3d=True)): `model.update_filter_3d` on ALL
+    training cameras (every rank passes them all: no collective) before the first step, every `filter_every` iterations and
+    right after every densify / relocate / prune pass; the saved .ply holds the filtered scales and opacities.  The held-out
+    cameras never enter it.  100 iterations and the filter's variance 0.2 are the published values, not tuned here.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -208,6 +216,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         sh["densify_on"] = densify_on
     if screen_grad != "signed":
         sh["screen_grad"] = screen_grad
+    if filter_3d:
+        sh["filter_3d"] = True
     if load_ply is not None:
         model = gm.GS_model_with_param.from_ply(load_ply, dev, **sh)
     else:
@@ -216,6 +226,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     extent = data.get_camera_extent()
     gen = torch.Generator().manual_seed(seed)
     losses, iteration, t0 = [], 0, time.time()
+    if filter_3d:
+        model.update_filter_3d(P, K, wh)
     while iteration < iterations:
         order = torch.randperm(len(data), generator=gen)
         for b in range(0, len(order), batch_size):
@@ -279,6 +291,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     gm.allreduce_contribution(stats)
                 n_before, n_after = model.prune_by_contribution(stats, prune_contribution, prune_on)
                 log(f"iter {iteration:5d}  pruned by contribution (w_{prune_on} < {prune_contribution:g}): Gaussians {n_before} -> {n_after}")
+                if filter_3d:
+                    model.update_filter_3d(P, K, wh)
             if densify_from_iter <= iteration <= densify_until_iter and iteration % densification_interval == 0:
                 if densify == "mcmc":
                     model.relocate_and_grow_device(seed + iteration, cap_max)
@@ -288,6 +302,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     model.densify_and_prune_device(extent, seed=seed + iteration)
                 else:
                     model.densify_and_prune(extent)
+                if filter_3d:
+                    model.update_filter_3d(P, K, wh)
+            elif filter_3d and iteration % max(1, filter_every) == 0:
+                model.update_filter_3d(P, K, wh)
             if opacity_reset_interval and iteration % opacity_reset_interval == 0 and densify != "mcmc":
                 if densify == "device":
                     model.reset_opacity(reset_opacity_min, keep_optimizer=True)
@@ -363,6 +381,12 @@ def build_parser():
     ap.add_argument("--distortion-reg", type=float, default=0.0, metavar="L",
                     help="weight of the mean per-pixel depth distortion (Mip-NeRF 360 / 2DGS) in the loss (0: off; not tuned here)")
     ap.add_argument("--distortion-from", type=int, default=0, metavar="I", help="with --distortion-reg: the first iteration that carries the term")
+    ap.add_argument("--filter-3d", action="store_true",
+                    help="Mip-Splatting's 3-D smoothing filter: every Gaussian low-pass filtered in world space by the highest rate a training "
+                         "camera samples it at, its mass kept; full Mip-Splatting is --filter-3d --centres subpixel --dilation 0.1 --antialias")
+    ap.add_argument("--filter-every", type=int, default=100, metavar="N",
+                    help="with --filter-3d: recompute the filter every N iterations (and after every densify / relocate / prune pass); "
+                         "100 is the published cadence, not tuned here")
     return ap
 
 
@@ -399,7 +423,8 @@ if __name__ == "__main__":
                       antialias=a.antialias, cap_max=a.cap_max, noise_lr=a.noise_lr, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg,
                       prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam,
                       test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names,
-                      screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from)
+                      screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from,
+                      filter_3d=a.filter_3d, filter_every=a.filter_every)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -892,6 +892,43 @@ int gcp_blend_distort_backward(const int32_t* start_xy, const int32_t* end_xy, c
                                const float* grad_dist, float* grad_mean, float* grad_vinv, float* grad_opacity,
                                float* grad_depth, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the 3-D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024; csrc/gcp_filter3d.hip) ---------------------------
+ * A stage in FRONT of the projection: every Gaussian is low-pass filtered in world space by an isotropic Gaussian of size
+ * filter[i] = phi >= 0 (the caller forms it from the sampling rate: phi = sqrt(0.2) / rate in the published code) and its
+ * opacity is scaled so that it keeps its mass.  One thread per Gaussian in a grid-stride loop of at most 4096 blocks of 256;
+ * no atomics, one writer per output word, no arithmetic that depends on a thread's position: the same bits whatever the
+ * launch shape.  No device->host read, no stream wait, no allocation.  Every entry point validates before any HIP call (a
+ * negative size or one above INT32_MAX, a non-finite near_z or margin, margin < 0, NULL with rows to process:
+ * GCP_ERR_INVALID_ARGUMENT); n_gauss == 0, and for the rate n_cams == 0, is a no-op that touches nothing and launches nothing.
+ *
+ * gcp_filter3d_rate: mean f32[n_gauss,3], P f32[n_cams,3,4] world->camera, K f32[n_cams,3,3], wh i32[n_cams,2] = (W, H) ->
+ * rate f32[n_gauss].  For camera c, in float32 with every sum left to right: t = P_c [mean; 1], u = fx t.x / t.z + cx,
+ * v = fy t.y / t.z + cy with fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2] (the skew K[0][1] is ignored).  The
+ * camera SEES the Gaussian iff t.z > near_z and -margin W <= u <= (1 + margin) W and -margin H <= v <= (1 + margin) H (a NaN
+ * is not seen); rate[i] = max over the seeing cameras of max(fx, fy) / t.z, 0 where none sees it.  Mip-Splatting's values:
+ * near_z = 0.2, margin = 0.15.  The cameras are read through wave-uniform addresses, not staged: there is no chunk size.
+ *
+ * gcp_filter3d_apply: log_scale f32[n_gauss,3] (v), opacity_logit f32[n_gauss] (x), filter f32[n_gauss] (phi) ->
+ * log_scale_out f32[n_gauss,3] (v'), opacity_out f32[n_gauss] (x').  With r_j = phi^2 e^(-2 v_j):
+ *   v'_j = v_j + 1/2 log1p(r_j)                      (s'^2 = s^2 + phi^2)
+ *   log c = -1/2 sum_j log1p(r_j)                    (c = sqrt(prod s^2 / prod s'^2) in (0, 1])
+ *   x' = x + log c - log1p(e^x (1 - c))              (sigmoid(x') = sigmoid(x) c),  1 - c = -expm1(log c)
+ * in float32.  A row with phi == 0 is copied bit for bit.  Finite for v in [-30, 10], phi in {0} u [1e-6, 1e2], x in
+ * [-20, 20].  The outputs must not alias the inputs.  36 bytes per row.
+ *
+ * gcp_filter3d_apply_backward: the same three inputs and g_log_scale_out f32[n_gauss,3], g_opacity_out f32[n_gauss] (the
+ * loss's gradients with respect to v', x') -> g_log_scale f32[n_gauss,3], g_opacity f32[n_gauss]; every row is written,
+ * every intermediate is recomputed.  With u = e^x (1 - c):
+ *   g_x = g_x' / (1 + u),   g_logc = g_x' (1 + e^x) / (1 + u),   g_v_j = g_v'_j / (1 + r_j) + g_logc (r_j / (1 + r_j)).
+ * phi carries no gradient.  A row with phi == 0 passes the gradients through bit for bit.  52 bytes per row. */
+int gcp_filter3d_rate(const float* mean, const float* P, const float* K, const int32_t* wh, int64_t n_gauss, int64_t n_cams,
+                      float near_z, float margin, float* rate, void* stream);
+int gcp_filter3d_apply(const float* log_scale, const float* opacity_logit, const float* filter, int64_t n_gauss,
+                       float* log_scale_out, float* opacity_out, void* stream);
+int gcp_filter3d_apply_backward(const float* log_scale, const float* opacity_logit, const float* filter,
+                                const float* g_log_scale_out, const float* g_opacity_out, int64_t n_gauss, float* g_log_scale,
+                                float* g_opacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ Row f4 of SURVEY.md §8: this is caller integration, PyTorch on the GPU around t
 This module holds the model and dataset classes and the reference's small helpers.  What the model calls lives next to
 it and is re-exported from here under the names it always had: the camera projection (projection.py: `camera_inputs`),
 the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
-(density.py: `accumulate_screen_grads`).  Differences from the reference's class, all deliberate (those of the projection:
+(density.py: `accumulate_screen_grads`) and the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
+`apply_filter`).  Differences from the reference's class, all deliberate (those of the projection:
 projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
@@ -26,6 +27,7 @@ from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 from .cuda_kernel import paint as _paint
 from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
+from .filter3d import apply_filter, filter_from_rate, sampling_rate
 from .loss import ImageMetrics, image_metrics, psnr_from_mse, splat_loss
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
@@ -40,12 +42,15 @@ __all__ = [
     "ImageMetrics",
     "accumulate_screen_grads",
     "allreduce_contribution",
+    "apply_filter",
     "camera_inputs",
+    "filter_from_rate",
     "gather_metrics",
     "image_metrics",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
     "mean_neighbour_distance",
+    "sampling_rate",
     "splat_loss",
     "split_cameras",
 ]
@@ -170,7 +175,7 @@ class GS_model_with_param(torch.nn.Module):
                  position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.025, scaling_lr=0.005,
                  rotation_lr=0.001, c_00=1.77, L_max=2, lr=0.1, reference_layout=False, sh_frame="camera",
                  active_sh_degree=None, centres="pixel", cov_dilation=None, clamp_colour=False, densify_on="position",
-                 antialias=False, adam="tensor", screen_grad="signed"):
+                 antialias=False, adam="tensor", screen_grad="signed", filter_3d=False):
         """L_max (0..3): the SH degree the colour parameter stores, (N, (L_max+1)^2, 3).  active_sh_degree (default L_max):
         the degree that is evaluated and trained; `oneup_sh_degree()` raises it.  sh_frame, centres, cov_dilation,
         clamp_colour, antialias: see `camera_inputs`; `forward`, `render` and `camera_inputs` of the model project with them.
@@ -192,8 +197,21 @@ class GS_model_with_param(torch.nn.Module):
         adam: the optimiser step on the GPU (`HipAdam`).  "tensor" (the default): one kernel per parameter tensor, step counts
         on the host.  "fused": all five tensors in one call, step counts and rates on the device (capturable).  "sparse": the
         fused call with the row mask `train_step(visible)` is given — rows outside it keep parameters and moments, as the
-        sparse Adam of other 3DGS trainers; GPU only."""
+        sparse Adam of other 3DGS trainers; GPU only.
+        filter_3d=True: Mip-Splatting's 3-D smoothing filter, the other half of `antialias` (csrc/gcp_filter3d.hip; GPU only).
+        `update_filter_3d(P, K, wh)` computes a per-Gaussian filter size from ALL training cameras and keeps it in
+        `self.filter_3d` (a plain tensor: no Parameter, not in the optimiser; the option itself is `self.use_filter_3d`); every draw (`forward`, `render`, `evaluate`,
+        `contribution`, `camera_inputs`) then projects `apply_filter(variance_scale, opacity, filter_3d)` in place of the raw
+        two, and the gradients reach the raw parameters through it.  Like antialias it changes what the blend sees, not the
+        parameters: the pruning thresholds, `reset_opacity`, the MCMC weights and noise and the split sizes all keep reading
+        the raw values; `save_ply` bakes the filter in by default.  The filter is stale before the first `update_filter_3d` and
+        after every pass that changes the row set (`densify_and_prune`, `densify_and_prune_device`, `relocate_and_grow_device`,
+        `prune_rows`, `prune_by_contribution`): the next draw raises until `update_filter_3d` has run again — it is never
+        carried through a gather, new rows sit at new positions."""
         super().__init__()
+        if not isinstance(filter_3d, bool):
+            raise ValueError(f"filter_3d: True or False, got {filter_3d!r}")
+        self.use_filter_3d, self.filter_3d = filter_3d, None
         if adam not in ADAM_MODES:
             raise ValueError(f"adam: 'tensor', 'fused' or 'sparse', got {adam!r}")
         if adam == "sparse" and not mean.is_cuda:
@@ -323,6 +341,7 @@ class GS_model_with_param(torch.nn.Module):
             if extra is not None:
                 rows = torch.cat((rows, extra[name]), dim=0)
             setattr(self, name, rows)
+        self.filter_3d = None  # the row set changed: `update_filter_3d` again
 
     def _rows(self, mask, repeat=1):
         out = {k: getattr(self, k).data[mask].repeat(repeat, *([1] * (getattr(self, k).dim() - 1)))
@@ -414,6 +433,7 @@ class GS_model_with_param(torch.nn.Module):
         for k, (exp_avg, exp_avg_sq) in moments.items():
             self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
         self._zero_density_stats(m)
+        self.filter_3d = None  # the row set changed: `update_filter_3d` again
         return n, m
 
     # ---- the MCMC strategy (3DGS-MCMC, Kheradmand et al. 2024; csrc/gcp_mcmc.hip) -----------------------------------------
@@ -459,6 +479,7 @@ class GS_model_with_param(torch.nn.Module):
         for k, (exp_avg, exp_avg_sq) in moments.items():
             self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
         self._zero_density_stats(m)
+        self.filter_3d = None  # the row set changed: `update_filter_3d` again
         return n, m
 
     # ---- prune by what a Gaussian paints (csrc/gcp_contrib.hip) -------------------------------------------------------------
@@ -515,6 +536,7 @@ class GS_model_with_param(torch.nn.Module):
         for k, (exp_avg, exp_avg_sq) in moments.items():
             self._optimizer.state[getattr(self, k)] = {"step": states[k]["step"], "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
         self._zero_density_stats(m)
+        self.filter_3d = None  # the row set changed: `update_filter_3d` again
         return n, m
 
     def prune_by_contribution(self, stats, threshold=0.01, on="max"):
@@ -570,18 +592,52 @@ class GS_model_with_param(torch.nn.Module):
         accumulate_screen_grads(grad, index, scale, self.screen_grads_norm, self.screen_grads_views)
 
     # ---- forward (:277-460) ------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def update_filter_3d(self, P, K, wh, variance=0.2):
+        """Compute and keep `self.filter_3d` float32 (N,), the 3-D filter's size per Gaussian, from the cameras (P, K, wh):
+        phi = sqrt(variance) / rate, rate = the largest focal / depth over the cameras that see the Gaussian
+        (`sampling_rate`: depth > 0.2, centre within the image widened by 15 %), the rows no camera sees getting the largest phi
+        of the seen ones (`filter_from_rate`).  Pass ALL training cameras, not a batch; under camera data parallelism every
+        rank passes the full camera arrays (they are small), so there is no collective and every rank gets the same bits.
+        Call it before the first draw, every ~100 iterations (the means move) and after every pass that changes the row set.
+        variance = 0.2 and that cadence are Mip-Splatting's published values, not tuned here.  One kernel and a few torch ops,
+        nothing read back.  Returns the tensor."""
+        if not self.use_filter_3d:
+            raise RuntimeError("update_filter_3d: this model was built without filter_3d=True")
+        if not self.mean.is_cuda:
+            raise RuntimeError("the 3-D filter is a HIP kernel: tensors must live on the GPU (no CPU path)")
+        self.filter_3d = filter_from_rate(sampling_rate(self.mean.data, P, K, wh), variance)
+        return self.filter_3d
+
+    def _filtered(self):
+        """(variance_scale, opacity) as the blend sees them: through `apply_filter` under filter_3d=True, the raw parameters
+        otherwise."""
+        if not self.use_filter_3d:
+            return self.variance_scale, self.opacity
+        if not self.mean.is_cuda:
+            raise RuntimeError("the 3-D filter is a HIP kernel: tensors must live on the GPU (no CPU path)")
+        if self.filter_3d is None or self.filter_3d.shape[0] != self.mean.shape[0]:
+            raise RuntimeError("filter_3d=True but the filter is stale (never computed, or the row set changed since): call "
+                               "update_filter_3d(P, K, wh) with all training cameras before drawing")
+        return apply_filter(self.variance_scale, self.opacity, self.filter_3d)
+
     def camera_inputs(self, P, K, wh, with_depth=False, capture_safe=False):
         if capture_safe and self.densify_on == "screen":
             raise RuntimeError("densify_on='screen' does not support capture-safe lists: its statistic is collected per kept list entry")
-        return camera_inputs(self.mean, self.variance_q, self.variance_scale, self.opacity, self.color, P, K, wh,
+        variance_scale, opacity = self._filtered()
+        return camera_inputs(self.mean, self.variance_q, variance_scale, opacity, self.color, P, K, wh,
                              self.variance_pixel_tile_max_width, self.active_sh_degree, capture_safe=capture_safe,
                              with_depth=with_depth, sh_frame=self.sh_frame, centres=self.centres, cov_dilation=self.cov_dilation,
                              clamp_colour=self.clamp_colour, antialias=self.antialias)
 
     # ---- scene files (ply_io) ------------------------------------------------------------------------------------
-    def save_ply(self, path, convention="3dgs"):
+    def save_ply(self, path, convention="3dgs", bake_filter=True):
         """The scene as a standard 3DGS .ply (ply_io.save_ply).  Other renderers evaluate the SH basis on world-space
-        directions: a model in the camera frame with an active degree > 0 is saved with a warning."""
+        directions: a model in the camera frame with an active degree > 0 is saved with a warning.
+        Under filter_3d=True the file holds, by default, the FILTERED scales and opacities (`apply_filter` on the current
+        `filter_3d`; a stale filter raises), so a standard viewer shows what was trained and `from_ply` into a model without
+        the filter draws the same images; bake_filter=False writes the raw parameters.  Without filter_3d the argument has no
+        effect and the file is byte for byte what it always was."""
         from . import ply_io
 
         if self.sh_frame != "world" and self.active_sh_degree > 0:
@@ -589,8 +645,11 @@ class GS_model_with_param(torch.nn.Module):
 
             warnings.warn("save_ply: this model evaluates its SH colour on camera-frame directions (sh_frame='camera'); other "
                           "renderers use world-space directions, so the view dependence of the saved scene will be wrong there")
-        ply_io.save_ply(path, self.mean.data, self.variance_q.data, self.variance_scale.data, self.opacity.data, self.color.data,
-                        convention=convention)
+        variance_scale, opacity = self.variance_scale.data, self.opacity.data
+        if self.use_filter_3d and bake_filter:
+            with torch.no_grad():
+                variance_scale, opacity = self._filtered()
+        ply_io.save_ply(path, self.mean.data, self.variance_q.data, variance_scale, opacity, self.color.data, convention=convention)
 
     @classmethod
     def from_ply(cls, path, device="cpu", convention="3dgs", **model_kwargs):
