@@ -38,6 +38,10 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --distortion-reg 100 --distortion-from 300
                                                              # from iteration 300 the loss gains 100 * the mean per-pixel depth
                                                              # distortion (Mip-NeRF 360 / 2DGS): pulls each ray's weights together
+    python examples/train_cameras.py --colmap DIR --exposure --save-exposure exposure.json
+                                                             # one learned 3 x 4 colour affine per training photograph, applied
+                                                             # to the render inside the loss kernels (upstream 3DGS's exposure
+                                                             # compensation), written as image name -> matrix
     python examples/train_cameras.py --test-every 8 --eval-every 100 --eval-json eval.json
                                                              # hold out every 8th camera (sorted by name, the llffhold convention),
                                                              # report PSNR / SSIM / L1 on them every 100 iterations and at the end
@@ -107,7 +111,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           sh_frame="camera", sh_every=0, save_ply=None, load_ply=None, centres="pixel", dilation=None, clamp_colour=False,
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
-          screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100):
+          screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
+          exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -155,6 +160,14 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     training cameras (every rank passes them all: no collective) before the first step, every `filter_every` iterations and
     right after every densify / relocate / prune pass; the saved .ply holds the filtered scales and opacities.  The held-out
     cameras never enter it.  100 iterations and the filter's variance 0.2 are the published values, not tuned here.
+    `exposure`: per-camera exposure compensation (`gs_model.CameraExposure`): one 3 x 4 colour affine per TRAINING camera,
+    initialised to the identity, applied to the render inside the loss kernels (`splat_loss(exposure=)`) and trained by an Adam
+    group of its own on the rows of the cameras a step drew (`exposure_lr_init` -> `exposure_lr_final` over 30 000 steps: the
+    published rates of upstream 3DGS, not tuned here); under `world` > 1 its gradient is summed and the drawn cameras OR-ed over
+    the ranks first.  The held-out cameras have no learned exposure: they are evaluated with the identity, and every eval
+    record then says "exposure": "identity".  `save_exposure`: write the matrices there as one JSON object, image name ->
+    3 x 4 list (rank 0).  Scene brightness times exposure gain is not pinned (as upstream) and no regulariser is added.  With
+    exposure=False (the default) no step changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -167,6 +180,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
     held = None
+    train_names = None if names is None else [str(n) for n in names]
     if test_every:
         names = [f"{i:06d}" for i in range(P.shape[0])] if names is None else list(names)
         if len(names) != P.shape[0]:
@@ -181,6 +195,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             if target_alpha is not None:
                 held["targets"] = held["targets"] + (1 - target_alpha[out]) * held["background"][None, :, None, None]
         P, K, wh, targets = P[keep], K[keep], wh[keep], targets[keep]
+        train_names = [str(names[i]) for i in train_idx]
         target_alpha = None if target_alpha is None else target_alpha[keep]
 
     def evaluate_held_out():
@@ -199,6 +214,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             evals.append({"iteration": iteration, "split": "test", "views": n_test, "gaussians": int(model.mean.shape[0]),
                           "psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim)), "l1": float(np.mean(l1)),
                           "per_image": {name: {"psnr": p, "ssim": s, "l1": e} for name, p, s, e in zip(held["names"], psnr, ssim, l1)}})
+            if ce is not None:  # no exposure is learned for a held-out camera
+                evals[-1]["exposure"] = "identity"
 
     torch.manual_seed(seed)  # densification draws samples: every rank must draw the same ones
     n = start.shape[0]
@@ -222,6 +239,9 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         model = gm.GS_model_with_param.from_ply(load_ply, dev, **sh)
     else:
         model = gm.GS_model_with_param(start.clone(), q, scale, opacity, L_max=sh_degree, **sh)
+    ce = None
+    if exposure:
+        ce = gm.CameraExposure(P.shape[0], names=train_names, device=dev, lr_init=exposure_lr_init, lr_final=exposure_lr_final)
     data = gm.GS_dataset(P, K, wh, list(range(P.shape[0])))
     extent = data.get_camera_extent()
     gen = torch.Generator().manual_seed(seed)
@@ -251,7 +271,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     target = targets[sel]
                     if bg is not None and target_alpha is not None:
                         target = target + (1 - target_alpha[sel]) * bg[None, :, None, None]
-                loss = gm.splat_loss(images, target, loss_lamda) * (mine.numel() / idx.numel())
+                if ce is None:
+                    loss = gm.splat_loss(images, target, loss_lamda) * (mine.numel() / idx.numel())
+                else:
+                    loss = gm.splat_loss(images, target, loss_lamda, exposure=ce.rows(kept)) * (mine.numel() / idx.numel())
                 if dist is not None:  # the geometric regulariser: the mean per-pixel depth distortion of this rank's share
                     loss = loss + distortion_reg * dist.mean() * (mine.numel() / idx.numel())
                 if densify == "mcmc":  # the regularisers that let opacities die and keep scales small; the whole term on every rank's share
@@ -259,6 +282,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                                    + scale_reg * torch.exp(model.variance_scale).mean()) * (mine.numel() / idx.numel())
                 loss.backward()
             else:  # more ranks than cameras in this batch
+                kept = []
                 loss, grad_iter = torch.zeros((), device=dev), torch.zeros(model.mean.shape[0], dtype=torch.bool, device=dev)
             if world > 1:
                 grad_iter = model.allreduce_grads(grad_iter)
@@ -271,6 +295,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     torch.distributed.all_reduce(loss)
             model.param_iter_update(grad_iter)
             model.train_step(visible=grad_iter)
+            if ce is not None:
+                drawn = ce.allreduce_grads(kept) if world > 1 else kept
+                ce.set_lr(iteration)
+                ce.step(drawn)
             if densify == "mcmc":
                 model.add_position_noise(seed + iteration, noise_lr)
             iteration += 1
@@ -324,6 +352,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     log(f"{iteration} iterations in {time.time() - t0:.1f} s")
     if save_ply is not None and rank == 0:
         model.save_ply(save_ply)
+    if ce is not None and save_exposure is not None and rank == 0:
+        ce.save_json(save_exposure)
     return model, losses
 
 
@@ -387,6 +417,12 @@ def build_parser():
     ap.add_argument("--filter-every", type=int, default=100, metavar="N",
                     help="with --filter-3d: recompute the filter every N iterations (and after every densify / relocate / prune pass); "
                          "100 is the published cadence, not tuned here")
+    ap.add_argument("--exposure", action="store_true",
+                    help="learn one 3 x 4 colour affine per training camera, applied to the render inside the loss kernels "
+                         "(upstream 3DGS's exposure compensation); held-out cameras are evaluated with the identity")
+    ap.add_argument("--exposure-lr-init", type=float, default=0.01, help="with --exposure: the first learning rate (upstream's, not tuned here)")
+    ap.add_argument("--exposure-lr-final", type=float, default=0.001, help="with --exposure: the rate after 30 000 steps (upstream's)")
+    ap.add_argument("--save-exposure", default=None, metavar="PATH", help="with --exposure: write the matrices as JSON, image name -> 3 x 4 list")
     return ap
 
 
@@ -395,6 +431,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if (a.eval_every or a.eval_json) and not a.test_every:
         ap.error("--eval-every and --eval-json need --test-every N with N > 0")
+    if a.save_exposure and not a.exposure:
+        ap.error("--save-exposure needs --exposure")
     if a.antialias and not (a.dilation is not None and a.dilation > 0):
         ap.error("--antialias requires --dilation F with F > 0")
     prune_at = tuple(int(v) for v in a.prune_at.split(",") if v)
@@ -424,7 +462,8 @@ if __name__ == "__main__":
                       prune_contribution=a.prune_contribution, prune_at=prune_at, prune_on=a.prune_on, adam=a.adam,
                       test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names,
                       screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from,
-                      filter_3d=a.filter_3d, filter_every=a.filter_every)
+                      filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
+                      exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -686,6 +686,37 @@ int gcp_ssim_l1_backward(const float* img1, const float* img2, const float* dm_d
 int gcp_image_metrics(const float* img, const float* ref, int64_t images, int32_t channels, int32_t height, int32_t width,
                       const float* window11_host, float c1, float c2, int32_t flags, float* partial, double* out, void* stream);
 
+/* ---- per-camera exposure compensation fused into the loss and the metrics ------------------------------------------------
+ * img, ref: float[images][3][height][width] (three channels are implied); exposure: DEVICE float[images][3][4], one colour
+ * affine per image.  The loss and the metrics are those above of y against ref, with
+ *   y_c = E[c][0] x_0 + E[c][1] x_1 + E[c][2] x_2 + E[c][3]
+ * formed by one fixed chain of fused multiply-adds as the tiles are staged; y is never written to memory, and E = [I | 0]
+ * gives the bits of the plain entry points.
+ * gcp_ssim_l1_forward_exposure: partial and the three maps (with respect to y; all three or none) as gcp_ssim_l1_forward
+ * with planes = 3 * images, so partial is float[gcp_ssim_blocks(3 * images, ...)][2] in the same order.
+ * gcp_ssim_l1_backward_exposure: with g_c = scales[0] * dSum(SSIM)/dy_c + scales[1] * sign(y_c - b_c),
+ *   grad_img[i][k] = sum_c E[i][c][k] g_c (may be NULL),
+ *   grad_exposure[i][c][k] = sum over the pixels of image i of g_c x_k, [i][c][3] = sum of g_c (may be NULL; every entry
+ *   is written otherwise).  One block per (image, tile) writes twelve float sums to partial_e (float[gcp_exposure_blocks()][12],
+ *   needed with grad_exposure); one block per image adds them in double in a fixed order.  No atomics: the same bits on
+ *   every run, and an image's gradients depend on that image alone.
+ * gcp_image_metrics_exposure: gcp_image_metrics of y; with GCP_METRICS_CLAMP y (after the compensation) is clamped.
+ * No allocation and no device->host read (capturable).  GCP_ERR_INVALID_ARGUMENT before any HIP call: images < 0, height or
+ * width < 6, a NULL window, an unknown flag bit; with images > 0 more than 2^31 - 1 blocks, a NULL pointer among the
+ * required arrays, a partial set of maps, grad_img and grad_exposure both NULL.  images == 0 is a no-op after the scalar
+ * checks.  gcp_exposure_blocks: images * tiles, 0 on bad input. */
+int64_t gcp_exposure_blocks(int64_t images, int32_t height, int32_t width);
+int gcp_ssim_l1_forward_exposure(const float* img, const float* ref, const float* exposure, int64_t images, int32_t height,
+                                 int32_t width, const float* window11_host, float c1, float c2, float* dm_dmu1, float* dm_de11,
+                                 float* dm_de12, float* partial, void* stream);
+int gcp_ssim_l1_backward_exposure(const float* img, const float* ref, const float* exposure, const float* dm_dmu1,
+                                  const float* dm_de11, const float* dm_de12, int64_t images, int32_t height, int32_t width,
+                                  const float* window11_host, const float* scales, float* grad_img /* may be NULL */,
+                                  float* partial_e, float* grad_exposure /* may be NULL */, void* stream);
+int gcp_image_metrics_exposure(const float* img, const float* ref, const float* exposure, int64_t images, int32_t height,
+                               int32_t width, const float* window11_host, float c1, float c2, int32_t flags, float* partial,
+                               double* out, void* stream);
+
 /* ---- the caller's optimiser step ---------------------------------------------------------
  * torch.optim.Adam's update (no weight decay, no amsgrad; gs_model.py:43-47, :64-67) of one parameter tensor of n
  * floats, in place: exp_avg = beta1 exp_avg + (1 - beta1) grad; exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) grad^2;

@@ -116,6 +116,14 @@ SIGNATURES = {
     # img, ref, images, channels, height, width, host window, c1, c2, GCP_METRICS_* flags, partial, out (double), stream
     "gcp_image_metrics": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float, _i32]
                           + [_c_void_p] * 3),
+    # per-camera exposure (device float[images][3][4] after img, ref; three channels implied): the loss forward and backward
+    # (..., scales, grad_img or NULL, partial_e, grad_exposure or NULL, stream) and the metrics on the compensated render
+    "gcp_exposure_blocks": (_i64, [_i64, _i32, _i32]),
+    "gcp_ssim_l1_forward_exposure": (ctypes.c_int, [_c_void_p] * 3 + [_i64, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float]
+                                     + [_c_void_p] * 5),
+    "gcp_ssim_l1_backward_exposure": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32] + [_c_void_p] * 6),
+    "gcp_image_metrics_exposure": (ctypes.c_int, [_c_void_p] * 3 + [_i64, _i32, _i32, _c_void_p, ctypes.c_float, ctypes.c_float, _i32]
+                                   + [_c_void_p] * 3),
     "gcp_project_backward": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 10),
     "gcp_project_gather_depth": (ctypes.c_int, [_c_void_p, _c_void_p, _i64] + [_c_void_p] * 12),
     "gcp_project_backward_depth": (ctypes.c_int, [_c_void_p] * 7 + [_i64, _i32, _i32] + [_c_void_p] * 11),

@@ -277,6 +277,299 @@ __global__ __launch_bounds__(kThreads) void k_metrics_fold(const float* __restri
   if (threadIdx.x < 3) out[3 * (i64)blockIdx.x + threadIdx.x] = s_acc[threadIdx.x][0] / count;
 }
 
+// ---- per-camera exposure compensation -------------------------------------------------------------------
+// One learned 3 x 4 colour affine per image, applied to the render before the loss: y_c = E[c][0] x_0 + E[c][1] x_1 +
+// E[c][2] x_2 + E[c][3].  y is never written to memory: it is formed as the tile is staged (reflect padding commutes with a
+// pointwise map), and the backward forms it again from x.  Siblings of the kernels above, whose text stays as it is.
+
+// THE compensated value: three fused multiply-adds in this order, wherever y is needed (forward staging, the backward's
+// 2 y g1 and sign(y - b), the metrics), so that all of them see the same bits.  Exact for E = [I | 0]: 1 * x_c + 0 + 0 + 0.
+__device__ __forceinline__ float exposure_apply(const float* __restrict__ e, float x0, float x1, float x2) {
+  return __fmaf_rn(e[0], x0, __fmaf_rn(e[1], x1, __fmaf_rn(e[2], x2, e[3])));
+}
+
+// y_c at offset o of an image whose three planes are `stride` floats apart; e: row c of the image's matrix.
+__device__ __forceinline__ float exposure_stage(const float* __restrict__ x, i64 stride, i64 o, const float* __restrict__ e) {
+  const float x0 = x[o], x1 = x[o + stride], x2 = x[o + 2 * stride];
+  return exposure_apply(e, x0, x1, x2);
+}
+
+// k_ssim_l1_fwd with y staged in place of img1: grid, tile, LDS layout and partial index are its own (block = plane * tiles +
+// tile, plane = 3 * image + c), so the host adds the block sums in the same order.  The two extra channel loads per halo
+// position re-read lines the blocks of the sibling planes fetch too.
+__global__ __launch_bounds__(kThreads) void k_ssim_l1_fwd_exposure(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                                  const float* __restrict__ exposure, int height, int width,
+                                                                  int tiles_x, int tiles_y, Window win, float c1, float c2,
+                                                                  float* __restrict__ dm_dmu1, float* __restrict__ dm_de11,
+                                                                  float* __restrict__ dm_de12, float* __restrict__ partial) {
+  __shared__ float s_a[kHH][kHW + 1], s_b[kHH][kHW + 1];
+  __shared__ float s_h[5][kHH][kTW + 1];
+  __shared__ float s_red[4];
+  const int tile = blockIdx.x % (tiles_x * tiles_y), plane = blockIdx.x / (tiles_x * tiles_y);
+  const int x0 = (tile % tiles_x) * kTW, y0 = (tile / tiles_x) * kTH;
+  const i64 stride = (i64)height * width;
+  const float* a = img1 + (i64)(plane / 3) * 3 * stride;  // the image's three planes
+  const float* b = img2 + (i64)plane * stride;
+  const float* e = exposure + 4 * (i64)plane;  // row c of image i: 12 i + 4 c
+  for (int i = threadIdx.x; i < kHH * kHW; i += kThreads) {
+    const int r = i / kHW, c = i % kHW;
+    // rows / columns past the image edge of a partial tile are clamped: their results are never used
+    const int y = reflect(min(y0 + r - kR, height - 1 + kR), height), x = reflect(min(x0 + c - kR, width - 1 + kR), width);
+    s_a[r][c] = exposure_stage(a, stride, (i64)y * width + x, e);
+    s_b[r][c] = b[(i64)y * width + x];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHH * kTW; i += kThreads) {  // blur along the row
+    const int r = i / kTW, c = i % kTW;
+    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float va = s_a[r][c + k], vb = s_b[r][c + k], w = win.w[k];
+      m1 += w * va, m2 += w * vb, e11 += w * (va * va), e22 += w * (vb * vb), e12 += w * (va * vb);
+    }
+    s_h[0][r][c] = m1, s_h[1][r][c] = m2, s_h[2][r][c] = e11, s_h[3][r][c] = e22, s_h[4][r][c] = e12;
+  }
+  __syncthreads();
+  float sum_ssim = 0.f, sum_l1 = 0.f;
+  const int c = threadIdx.x % kTW;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {  // blur along the column, two pixels per thread
+    const int r = threadIdx.x / kTW + half * (kTH / 2);
+    const int x = x0 + c, y = y0 + r;
+    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float w = win.w[k];
+      mu1 += w * s_h[0][r + k][c], mu2 += w * s_h[1][r + k][c], e11 += w * s_h[2][r + k][c], e22 += w * s_h[3][r + k][c],
+          e12 += w * s_h[4][r + k][c];
+    }
+    if (x < width && y < height) {
+      const float s1 = e11 - mu1 * mu1, s2 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
+      const float A = 2.f * mu1 * mu2 + c1, B = 2.f * s12 + c2, C = mu1 * mu1 + mu2 * mu2 + c1, D = s1 + s2 + c2;
+      const float den = C * D + 1e-12f, m = A * B / den;
+      sum_ssim += m;
+      sum_l1 += fabsf(s_a[r + kR][c + kR] - s_b[r + kR][c + kR]);
+      if (dm_dmu1) {
+        const i64 o = ((i64)plane * height + y) * width + x;
+        const float m_den = m / den;  // A B / den^2
+        dm_dmu1[o] = (2.f * mu2 * (B - A)) / den - m_den * (2.f * mu1 * (D - C));
+        dm_de11[o] = -m_den * C;
+        dm_de12[o] = 2.f * A / den;
+      }
+    }
+  }
+  const float t_ssim = block_sum(sum_ssim, s_red);
+  __syncthreads();
+  const float t_l1 = block_sum(sum_l1, s_red);
+  if (threadIdx.x == 0) partial[2 * (i64)blockIdx.x] = t_ssim, partial[2 * (i64)blockIdx.x + 1] = t_l1;
+}
+
+// One block per (image, tile), looping c = 0..2 over the LDS buffers of k_ssim_l1_bwd: g_c = dL/dy_c at the thread's two
+// pixels as k_ssim_l1_bwd forms it (with a := y_c, recomputed from x), then grad_x_k += E[c][k] g_c in six registers and the
+// channel's four products g_c x_k, g_c in per-thread sums, reduced per wave at once into a 12 x 4 LDS table (twelve live
+// accumulators would cost an occupancy step).  The twelve block sums (association of block_sum) share the one barrier after
+// the loop and go to partial_e[12 * block ..]; k_exposure_fold adds them per image.  grad (dL/dx) or partial_e may be NULL:
+// that output is skipped.  20 B read and 4 B written per pixel-channel, as the plain backward, plus 48 B per block.
+__global__ __launch_bounds__(kThreads) void k_ssim_l1_bwd_exposure(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                                  const float* __restrict__ exposure,
+                                                                  const float* __restrict__ dm_dmu1, const float* __restrict__ dm_de11,
+                                                                  const float* __restrict__ dm_de12, int height, int width, int tiles_x,
+                                                                  int tiles_y, Window win, const float* __restrict__ scales,
+                                                                  float* __restrict__ grad, float* __restrict__ partial_e) {
+  __shared__ float s_m[3][kHH][kHW + 1];
+  __shared__ float s_h[3][kHH][kTW + 1];
+  __shared__ float s_red[12][4];
+  const int tile = blockIdx.x % (tiles_x * tiles_y), image = blockIdx.x / (tiles_x * tiles_y);
+  const int x0 = (tile % tiles_x) * kTW, y0 = (tile / tiles_x) * kTH;
+  const i64 stride = (i64)height * width, base = (i64)image * 3 * stride;
+  const float* e = exposure + 12 * (i64)image;
+  const bool edge_x = x0 < kR + 1 || x0 + kTW + kR + 1 >= width;
+  const bool edge_y = y0 < kR + 1 || y0 + kTH + kR + 1 >= height;
+  const float s_ssim = scales[0], s_l1 = scales[1];
+  const int c = threadIdx.x % kTW;
+  float px[2][3], gx[2][3];
+  bool inside[2];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int x = x0 + c, y = y0 + threadIdx.x / kTW + half * (kTH / 2);
+    inside[half] = x < width && y < height;
+    const i64 o = base + (i64)y * width + x;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) px[half][k] = inside[half] ? img1[o + k * stride] : 0.f, gx[half][k] = 0.f;
+  }
+#pragma unroll 1  // one channel's registers at a time: unrolled, the three bodies overlap and cost an occupancy step
+  for (int ch = 0; ch < 3; ++ch) {
+    const i64 pbase = base + ch * stride;
+    for (int i = threadIdx.x; i < kHH * kHW; i += kThreads) {
+      const int r = i / kHW, cc = i % kHW;
+      const int y = y0 + r - kR, x = x0 + cc - kR;
+      const bool in = y >= 0 && y < height && x >= 0 && x < width;  // the maps are zero outside the image
+      const i64 o = pbase + (i64)y * width + x;
+      s_m[0][r][cc] = in ? dm_dmu1[o] : 0.f;
+      s_m[1][r][cc] = in ? dm_de11[o] : 0.f;
+      s_m[2][r][cc] = in ? dm_de12[o] : 0.f;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHH * kTW; i += kThreads) {
+      const int r = i / kTW, cc = i % kTW;
+      int p = x0 + cc;
+      asm volatile("" : "+v"(p));  // opaque per channel: the edge weights are formed again, not kept in registers across the loop
+      float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < kTaps; ++k) {
+        const float w = edge_x ? adjoint_weight(win, p, p + k - kR, width) : win.w[k];
+        h0 += w * s_m[0][r][cc + k], h1 += w * s_m[1][r][cc + k], h2 += w * s_m[2][r][cc + k];
+      }
+      s_h[0][r][cc] = h0, s_h[1][r][cc] = h1, s_h[2][r][cc] = h2;
+    }
+    __syncthreads();  // also: every read of s_m is done before the next channel is staged
+    float ge[4] = {0.f, 0.f, 0.f, 0.f};  // this thread's share of dL/dE[ch][0..3]
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int r = threadIdx.x / kTW + half * (kTH / 2);
+      int y = y0 + r;
+      asm volatile("" : "+v"(y));  // as p above
+      float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < kTaps; ++k) {
+        const float w = edge_y ? adjoint_weight(win, y, y + k - kR, height) : win.w[k];
+        g0 += w * s_h[0][r + k][c], g1 += w * s_h[1][r + k][c], g2 += w * s_h[2][r + k][c];
+      }
+      if (inside[half]) {
+        const float a = exposure_apply(e + 4 * ch, px[half][0], px[half][1], px[half][2]);
+        const float b = img2[pbase + (i64)y * width + x0 + c];
+        const float sgn = a > b ? 1.f : (a < b ? -1.f : 0.f);
+        const float g = s_ssim * (g0 + 2.f * a * g1 + b * g2) + s_l1 * sgn;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          gx[half][k] = __fmaf_rn(e[4 * ch + k], g, gx[half][k]);
+          ge[k] = __fmaf_rn(g, px[half][k], ge[k]);
+        }
+        ge[3] += g;
+      }
+    }
+    if (partial_e) {  // the wave's four sums of this channel; read after the barrier below the loop
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float v = ge[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if ((threadIdx.x & 63) == 0) s_red[4 * ch + k][threadIdx.x >> 6] = v;
+      }
+    }
+    // the next channel's row blur writes s_h only after the barrier that follows its staging: every read above is done by then
+  }
+  if (grad) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      if (inside[half]) {
+        const i64 o = base + (i64)(y0 + threadIdx.x / kTW + half * (kTH / 2)) * width + x0 + c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) grad[o + k * stride] = gx[half][k];
+      }
+    }
+  }
+  if (partial_e) {
+    __syncthreads();
+    if (threadIdx.x < 12) {
+      const float* s = s_red[threadIdx.x];
+      partial_e[12 * (i64)blockIdx.x + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+  }
+}
+
+// One block per image, in the pattern of k_metrics_fold: the image's `tiles` partials of k_ssim_l1_bwd_exposure (twelve floats
+// each, next to each other) added in double in a fixed order — strided per thread, then a fixed LDS tree, no atomics — and
+// rounded once: grad_exposure[image][12].  Every entry is written.
+__global__ __launch_bounds__(kThreads) void k_exposure_fold(const float* __restrict__ partial_e, i64 tiles, float* __restrict__ grad_exposure) {
+  __shared__ double s_acc[12][kThreads];
+  const float* p = partial_e + 12 * tiles * (i64)blockIdx.x;
+  double acc[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+  for (i64 i = threadIdx.x; i < tiles; i += kThreads) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) acc[k] += (double)p[12 * i + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) s_acc[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  for (int off = kThreads / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) s_acc[k][threadIdx.x] += s_acc[k][threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 12) grad_exposure[12 * (i64)blockIdx.x + threadIdx.x] = (float)s_acc[threadIdx.x][0];
+}
+
+// k_image_metrics on y: compensated as it is staged (exposure_stage), clamped after — the clamp applies to y.  The partials
+// and k_metrics_fold are those of k_image_metrics (three channels).
+__global__ __launch_bounds__(kThreads) void k_image_metrics_exposure(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                                    const float* __restrict__ exposure, int height, int width,
+                                                                    int tiles_x, int tiles_y, Window win, float c1, float c2, int clamp,
+                                                                    float* __restrict__ partial) {
+  __shared__ float s_a[kHH][kHW + 1], s_b[kHH][kHW + 1];
+  __shared__ float s_h[5][kHH][kTW + 1];
+  __shared__ float s_red[3][4];
+  const int tile = blockIdx.x % (tiles_x * tiles_y), plane = blockIdx.x / (tiles_x * tiles_y);
+  const int x0 = (tile % tiles_x) * kTW, y0 = (tile / tiles_x) * kTH;
+  const i64 stride = (i64)height * width;
+  const float* a = img1 + (i64)(plane / 3) * 3 * stride;
+  const float* b = img2 + (i64)plane * stride;
+  const float* e = exposure + 4 * (i64)plane;
+  const float lo = clamp ? 0.f : -__builtin_inff(), hi = clamp ? 1.f : __builtin_inff();
+  for (int i = threadIdx.x; i < kHH * kHW; i += kThreads) {
+    const int r = i / kHW, c = i % kHW;
+    // rows / columns past the image edge of a partial tile are clamped: their results are never used
+    const int y = reflect(min(y0 + r - kR, height - 1 + kR), height), x = reflect(min(x0 + c - kR, width - 1 + kR), width);
+    // all four loads first, then two selects against uniform bounds (+-inf without the clamp: the identity)
+    const float va = exposure_stage(a, stride, (i64)y * width + x, e), vb = b[(i64)y * width + x];
+    s_a[r][c] = va < lo ? lo : (va > hi ? hi : va);
+    s_b[r][c] = vb;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHH * kTW; i += kThreads) {  // blur along the row
+    const int r = i / kTW, c = i % kTW;
+    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float va = s_a[r][c + k], vb = s_b[r][c + k], w = win.w[k];
+      m1 += w * va, m2 += w * vb, e11 += w * (va * va), e22 += w * (vb * vb), e12 += w * (va * vb);
+    }
+    s_h[0][r][c] = m1, s_h[1][r][c] = m2, s_h[2][r][c] = e11, s_h[3][r][c] = e22, s_h[4][r][c] = e12;
+  }
+  __syncthreads();
+  float sum_ssim = 0.f, sum_l1 = 0.f, sum_sq = 0.f;
+  const int c = threadIdx.x % kTW;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {  // blur along the column, two pixels per thread
+    const int r = threadIdx.x / kTW + half * (kTH / 2);
+    const int x = x0 + c, y = y0 + r;
+    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      const float w = win.w[k];
+      mu1 += w * s_h[0][r + k][c], mu2 += w * s_h[1][r + k][c], e11 += w * s_h[2][r + k][c], e22 += w * s_h[3][r + k][c],
+          e12 += w * s_h[4][r + k][c];
+    }
+    if (x < width && y < height) {
+      const float s1 = e11 - mu1 * mu1, s2 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
+      const float A = 2.f * mu1 * mu2 + c1, B = 2.f * s12 + c2, C = mu1 * mu1 + mu2 * mu2 + c1, D = s1 + s2 + c2;
+      const float d = s_a[r + kR][c + kR] - s_b[r + kR][c + kR];
+      sum_ssim += A * B / (C * D + 1e-12f);
+      sum_l1 += fabsf(d);
+      sum_sq += d * d;
+    }
+  }
+  block_sum3(sum_ssim, sum_l1, sum_sq, s_red);
+  if (threadIdx.x == 0) {
+    float* p = partial + 3 * (i64)blockIdx.x;
+    p[0] = sum_ssim, p[1] = sum_l1, p[2] = sum_sq;
+  }
+}
+
 bool make_window(const float* window11_host, Window& w) {
   if (!window11_host) return false;
   for (int k = 0; k < kTaps; ++k) w.w[k] = window11_host[k];
@@ -338,6 +631,67 @@ int gcp_image_metrics(const float* img, const float* ref, int64_t images, int32_
   GCP_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_metrics_fold, dim3((unsigned)images), dim3(kThreads), 0, (hipStream_t)stream, (const float*)partial,
                      (i64)channels * tx * ty, (double)channels * (double)height * (double)width, out);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+int64_t gcp_exposure_blocks(int64_t images, int32_t height, int32_t width) { return gcp_ssim_blocks(images, height, width); }
+
+int gcp_ssim_l1_forward_exposure(const float* img, const float* ref, const float* exposure, int64_t images, int32_t height,
+                                 int32_t width, const float* window11_host, float c1, float c2, float* dm_dmu1, float* dm_de11,
+                                 float* dm_de12, float* partial, void* stream) {
+  Window win;
+  if (images < 0 || height < kR + 1 || width < kR + 1 || !make_window(window11_host, win)) return GCP_ERR_INVALID_ARGUMENT;
+  if (images == 0) return GCP_OK;
+  if (images > 0x7fffffff / 3) return GCP_ERR_INVALID_ARGUMENT;  // the plane count alone is past one grid
+  const int64_t blocks = gcp_ssim_blocks(3 * images, height, width);
+  if (blocks > 0x7fffffff || !img || !ref || !exposure || !partial) return GCP_ERR_INVALID_ARGUMENT;
+  if ((dm_dmu1 != nullptr) != (dm_de11 != nullptr) || (dm_dmu1 != nullptr) != (dm_de12 != nullptr)) return GCP_ERR_INVALID_ARGUMENT;
+  const int tx = (width + kTW - 1) / kTW, ty = (height + kTH - 1) / kTH;
+  hipLaunchKernelGGL(k_ssim_l1_fwd_exposure, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, img, ref, exposure,
+                     (int)height, (int)width, tx, ty, win, c1, c2, dm_dmu1, dm_de11, dm_de12, partial);
+  GCP_HIP(hipGetLastError());
+  return GCP_OK;
+}
+
+int gcp_ssim_l1_backward_exposure(const float* img, const float* ref, const float* exposure, const float* dm_dmu1,
+                                  const float* dm_de11, const float* dm_de12, int64_t images, int32_t height, int32_t width,
+                                  const float* window11_host, const float* scales, float* grad_img, float* partial_e,
+                                  float* grad_exposure, void* stream) {
+  Window win;
+  if (images < 0 || height < kR + 1 || width < kR + 1 || !make_window(window11_host, win)) return GCP_ERR_INVALID_ARGUMENT;
+  if (images == 0) return GCP_OK;
+  const int64_t blocks = gcp_exposure_blocks(images, height, width);
+  if (blocks > 0x7fffffff || !img || !ref || !exposure || !dm_dmu1 || !dm_de11 || !dm_de12 || !scales) return GCP_ERR_INVALID_ARGUMENT;
+  if ((!grad_img && !grad_exposure) || (grad_exposure && !partial_e)) return GCP_ERR_INVALID_ARGUMENT;
+  const int tx = (width + kTW - 1) / kTW, ty = (height + kTH - 1) / kTH;
+  hipLaunchKernelGGL(k_ssim_l1_bwd_exposure, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, img, ref, exposure, dm_dmu1,
+                     dm_de11, dm_de12, (int)height, (int)width, tx, ty, win, scales, grad_img, grad_exposure ? partial_e : nullptr);
+  GCP_HIP(hipGetLastError());
+  if (grad_exposure) {
+    hipLaunchKernelGGL(k_exposure_fold, dim3((unsigned)images), dim3(kThreads), 0, (hipStream_t)stream, (const float*)partial_e,
+                       (i64)tx * ty, grad_exposure);
+    GCP_HIP(hipGetLastError());
+  }
+  return GCP_OK;
+}
+
+int gcp_image_metrics_exposure(const float* img, const float* ref, const float* exposure, int64_t images, int32_t height,
+                               int32_t width, const float* window11_host, float c1, float c2, int32_t flags, float* partial,
+                               double* out, void* stream) {
+  Window win;
+  if (images < 0 || height < kR + 1 || width < kR + 1 || (flags & ~GCP_METRICS_CLAMP) || !make_window(window11_host, win))
+    return GCP_ERR_INVALID_ARGUMENT;
+  if (images == 0) return GCP_OK;
+  if (images > 0x7fffffff / 3) return GCP_ERR_INVALID_ARGUMENT;  // the plane count alone is past one grid
+  const int64_t blocks = gcp_ssim_blocks(images * 3, height, width);
+  if (blocks > 0x7fffffff || !img || !ref || !exposure || !partial || !out) return GCP_ERR_INVALID_ARGUMENT;
+  const int tx = (width + kTW - 1) / kTW, ty = (height + kTH - 1) / kTH;
+  hipLaunchKernelGGL(k_image_metrics_exposure, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, img, ref, exposure,
+                     (int)height, (int)width, tx, ty, win, c1, c2, (int)(flags & GCP_METRICS_CLAMP), partial);
+  GCP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_metrics_fold, dim3((unsigned)images), dim3(kThreads), 0, (hipStream_t)stream, (const float*)partial,
+                     (i64)3 * tx * ty, 3.0 * (double)height * (double)width, out);
   GCP_HIP(hipGetLastError());
   return GCP_OK;
 }

@@ -27,8 +27,9 @@ from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 from .cuda_kernel import paint as _paint
 from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
+from .exposure import CameraExposure
 from .filter3d import apply_filter, filter_from_rate, sampling_rate
-from .loss import ImageMetrics, image_metrics, psnr_from_mse, splat_loss
+from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
@@ -36,12 +37,14 @@ PARAM_NAMES = ("mean", "variance_q", "variance_scale", "opacity", "color")  # th
 ADAM_MODES = ("tensor", "fused", "sparse")
 
 __all__ = [
+    "CameraExposure",
     "GS_dataset",
     "GS_model_with_param",
     "HipAdam",
     "ImageMetrics",
     "accumulate_screen_grads",
     "allreduce_contribution",
+    "apply_exposure",
     "apply_filter",
     "camera_inputs",
     "filter_from_rate",
@@ -718,7 +721,7 @@ class GS_model_with_param(torch.nn.Module):
         return [images, *planes, names, grad_iter]
 
     @torch.no_grad()
-    def evaluate(self, P, K, wh, targets, background=None, batch_size=4, clamp=True):
+    def evaluate(self, P, K, wh, targets, background=None, batch_size=4, clamp=True, exposure=None):
         """Image quality on the cameras (P, K, wh) against `targets` (C, 3, H, W) -> `ImageMetrics` (mse, l1, ssim, psnr:
         float64 (C,) on the device), one entry per camera, in order.  The cameras are projected with the model's own options
         and painted as `render` paints them (`background`: float[3] on the device or None for black; the [1:, 1:] crop,
@@ -727,10 +730,14 @@ class GS_model_with_param(torch.nn.Module):
         A camera that sees no Gaussian is NOT dropped: its image is the background (or black) and it is measured like the
         others.  Nothing of the training state is touched: no `.grad`, no densification statistic, no optimiser state, no
         generator — a training run with evaluations in it takes the same steps as one without.  The metrics stay on the
-        device; the host reads are those of the projection and the binning.  GPU only.  LPIPS is not computed."""
+        device; the host reads are those of the projection and the binning.  GPU only.  LPIPS is not computed.
+        `exposure` (C, 3, 4): one colour affine per camera (`CameraExposure.rows`), handed to `image_metrics` batch by batch —
+        the render is compensated first and clamped after.  None (the default): no compensation, the plain kernel."""
         n_cam = P.shape[0]
         if targets.dim() != 4 or targets.shape[0] != n_cam:
             raise RuntimeError(f"targets: expected (C, 3, H, W) with one image per camera ({n_cam})")
+        if exposure is not None and tuple(exposure.shape) != (n_cam, 3, 4):
+            raise RuntimeError(f"exposure: expected (C, 3, 4) with one matrix per camera ({n_cam}), got {tuple(exposure.shape)}")
         batch_size = max(1, int(batch_size))
         with_depth = background is not None
         parts = []
@@ -748,7 +755,10 @@ class GS_model_with_param(torch.nn.Module):
                                    width, height, cam["depth"] if with_depth else None, background)
                 frames.append(frame)
             images = torch.stack(frames, dim=0)[:, 1:, 1:, :].permute(0, 3, 1, 2)
-            parts.append(image_metrics(images, targets[c:c + batch_size], clamp=clamp))
+            if exposure is None:
+                parts.append(image_metrics(images, targets[c:c + batch_size], clamp=clamp))
+            else:
+                parts.append(image_metrics(images, targets[c:c + batch_size], clamp=clamp, exposure=exposure[c:c + batch_size]))
         if not parts:
             empty = torch.zeros(0, dtype=torch.float64, device=self.mean.device)
             return ImageMetrics(empty, empty.clone(), empty.clone(), empty.clone())
