@@ -42,6 +42,10 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
                                                              # one learned 3 x 4 colour affine per training photograph, applied
                                                              # to the render inside the loss kernels (upstream 3DGS's exposure
                                                              # compensation), written as image name -> matrix
+    python examples/train_cameras.py --colmap DIR --undistort
+                                                             # the photographs resampled on the device, once, into the pinhole
+                                                             # cameras fitted to their lenses (what `colmap image_undistorter`
+                                                             # does for upstream 3DGS); K is then the fitted cameras'
     python examples/train_cameras.py --test-every 8 --eval-every 100 --eval-json eval.json
                                                              # hold out every 8th camera (sorted by name, the llffhold convention),
                                                              # report PSNR / SSIM / L1 on them every 100 iterations and at the end
@@ -93,15 +97,24 @@ def synthetic_scene(n_gauss, n_cam, width, height, seed, device, with_alpha=Fals
     return (start, P, K, wh, targets, alphas) if with_alpha else (start, P, K, wh, targets)
 
 
-def load_colmap(root, device, with_names=False):
-    """-> (xyz, P, K, wh, photographs (C, 3, H, W) in 0..1) [+ the image names with_names: what `split_cameras` sorts by]"""
+def load_colmap(root, device, with_names=False, undistort=False):
+    """-> (xyz, P, K, wh, photographs (C, 3, H, W) in 0..1) [+ the image names with_names: what `split_cameras` sorts by]
+    `undistort`: the photographs are uploaded as the bytes they decode to, one pinhole camera is fitted per image to its
+    camera's lens (`gs_model.fit_pinhole`: the source's size and principal point, the widest field of view without a blank
+    pixel), `gs_model.undistort` resamples them all in one HIP launch, and K is the fitted cameras' instead of the file's.
+    Every photograph is treated so, whether it is trained on or held out: they are photographs through the same lenses."""
     from PIL import Image
 
     from simplegaussiansplat_tk71_amd import colmap_io
 
-    xyz, P, K, wh, names = colmap_io.load_colmap_tensors(os.path.join(root, "sparse", "0"), device=device)
-    imgs = [torch.from_numpy(np.array(Image.open(os.path.join(root, "images", n)).convert("RGB"))).permute(2, 0, 1) for n in names]
-    photos = (torch.stack(imgs).float() / 255).to(device)
+    xyz, P, K, wh, names, *lenses = colmap_io.load_colmap_tensors(os.path.join(root, "sparse", "0"), device=device, lenses=undistort)
+    imgs = [torch.from_numpy(np.array(Image.open(os.path.join(root, "images", n)).convert("RGB"))) for n in names]
+    if undistort:
+        K_out = torch.stack([gm.fit_pinhole(lens)[0] for lens in lenses[0]])
+        photos = gm.undistort(torch.stack(imgs).to(device), lenses[0], K_out)
+        K = K_out.to(device=device, dtype=torch.float32)
+    else:
+        photos = (torch.stack([i.permute(2, 0, 1) for i in imgs]).float() / 255).to(device)
     return (xyz, P, K, wh, photos, list(names)) if with_names else (xyz, P, K, wh, photos)
 
 
@@ -360,6 +373,9 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--colmap", default=None, help="COLMAP root (sparse/0/*.bin + images/); default: synthetic scene")
+    ap.add_argument("--undistort", action="store_true",
+                    help="with --colmap: resample every photograph through its camera's lens distortion into a fitted pinhole camera "
+                         "(one HIP launch) and train on those; default: the distortion terms of cameras.bin are ignored")
     ap.add_argument("--gaussians", type=int, default=3000)
     ap.add_argument("--cameras", type=int, default=12)
     ap.add_argument("--width", type=int, default=160)
@@ -431,6 +447,8 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if (a.eval_every or a.eval_json) and not a.test_every:
         ap.error("--eval-every and --eval-json need --test-every N with N > 0")
+    if a.undistort and not a.colmap:
+        ap.error("--undistort needs --colmap DIR")
     if a.save_exposure and not a.exposure:
         ap.error("--save-exposure needs --exposure")
     if a.antialias and not (a.dilation is not None and a.dilation > 0):
@@ -449,7 +467,7 @@ if __name__ == "__main__":
             torch.distributed.init_process_group(a.backend)
     alphas, names, evals = None, None, []
     if a.colmap:
-        start, P, K, wh, targets, names = load_colmap(a.colmap, device, with_names=True)
+        start, P, K, wh, targets, names = load_colmap(a.colmap, device, with_names=True, undistort=a.undistort)
     elif background is not None:
         start, P, K, wh, targets, alphas = synthetic_scene(a.gaussians, a.cameras, a.width, a.height, 0, device, with_alpha=True)
     else:

@@ -960,6 +960,50 @@ int gcp_filter3d_apply_backward(const float* log_scale, const float* opacity_log
                                 const float* g_log_scale_out, const float* g_opacity_out, int64_t n_gauss, float* g_log_scale,
                                 float* g_opacity, void* stream);
 
+/* ---- lens distortion: photographs resampled into ideal pinhole cameras (csrc/gcp_undistort.hip) ------------------------
+ * What `colmap image_undistorter` does before training, on the device and for a whole batch in one launch: image b of
+ * `images`, taken through lens b, is resampled into the pinhole camera lens b names as its output, at the SAME size.
+ *
+ * lenses: f32[images][GCP_LENS_WORDS] on the device, one record per image:
+ *   word 0..3    fx, fy, cx, cy     the source photograph's intrinsics, in pixels; pixel centres at + 0.5
+ *   word 4..7    fx', fy', cx', cy' the output pinhole camera's
+ *   word 8..13   k1..k6             radial coefficients
+ *   word 14..15  p1, p2             tangential coefficients
+ *   word 16      kind               GCP_LENS_PINHOLE, GCP_LENS_POLYNOMIAL or GCP_LENS_FISHEYE as a float; any other value
+ *                                   is read as GCP_LENS_PINHOLE
+ *   word 17..19  not read
+ * With (x, y) normalised ideal coordinates and r^2 = x^2 + y^2:
+ *   GCP_LENS_POLYNOMIAL  radial = (1 + k1 r^2 + k2 r^4 + k3 r^6) / (1 + k4 r^2 + k5 r^4 + k6 r^6),
+ *                        x_d = x radial + 2 p1 x y + p2 (r^2 + 2 x^2),  y_d = y radial + 2 p2 x y + p1 (r^2 + 2 y^2)
+ *                        (COLMAP's SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV; OpenCV's rational model)
+ *   GCP_LENS_FISHEYE     theta = atan r, theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *                        (x_d, y_d) = (x, y) theta_d / r, and (x, y) itself at r = 0; k5, k6, p1, p2 are not read
+ *                        (COLMAP's OPENCV_FISHEYE, SIMPLE_RADIAL_FISHEYE, RADIAL_FISHEYE)
+ *   GCP_LENS_PINHOLE     (x_d, y_d) = (x, y)
+ * Output pixel (i, j) of image b, in float32 with the precise atanf, sqrtf and divisions:
+ *   x = (i + 0.5 - cx') / fx', y = (j + 0.5 - cy') / fy';  (u, v) = (fx x_d + cx, fy y_d + cy), clamped to
+ *   [0.5, width - 0.5] x [0.5, height - 0.5] (the source's edge is replicated; a NaN lands on the edge too);
+ *   dst[b][c][j][i] = the bilinear interpolation of channel c at (u - 0.5, v - 0.5) between the four pixels around it.
+ * gcp_undistort_u8:  src u8[images][height][width][3], the layout a JPEG decodes to; the result is divided by 255.
+ * gcp_undistort_f32: src f32[images][3][height][width].
+ * dst f32[images][3][height][width], every word written; it must not overlap src.
+ *
+ * One thread per output pixel in blocks of 64 x 4, the image in the grid's z dimension: at most 65535 images per grid, past
+ * which a block walks on by that stride, so `images` is bounded only by what can be indexed.  The record is read through
+ * wave-uniform addresses.  No atomics, no texture objects, no workspace, no device->host read; a pixel depends on its own
+ * coordinates and its image's record only: the same bits whatever the batch, its order or the launch shape.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: images < 0, height or width < 1, height * width > INT32_MAX, height >
+ * 4 * 65535 (the grid's y dimension), images * 12 * height * width > INT64_MAX, and with images > 0 a NULL src, lenses or
+ * dst.  images == 0 is a no-op that launches nothing. */
+#define GCP_LENS_WORDS 20
+#define GCP_LENS_PINHOLE 0
+#define GCP_LENS_POLYNOMIAL 1
+#define GCP_LENS_FISHEYE 2
+int gcp_undistort_u8(const uint8_t* src, const float* lenses, int64_t images, int32_t height, int32_t width, float* dst,
+                     void* stream);
+int gcp_undistort_f32(const float* src, const float* lenses, int64_t images, int32_t height, int32_t width, float* dst,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

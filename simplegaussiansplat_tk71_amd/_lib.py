@@ -167,11 +167,16 @@ SIGNATURES = {
     "gcp_filter3d_rate": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i64, ctypes.c_float, ctypes.c_float, _c_void_p, _c_void_p]),
     "gcp_filter3d_apply": (ctypes.c_int, [_c_void_p] * 3 + [_i64] + [_c_void_p] * 3),
     "gcp_filter3d_apply_backward": (ctypes.c_int, [_c_void_p] * 5 + [_i64] + [_c_void_p] * 3),
+    # lens distortion (gcp_undistort.hip): src (u8 [n,H,W,3] / f32 [n,3,H,W]), lenses f32[n][LENS_WORDS], images, height, width,
+    # dst f32[n,3,H,W], stream
+    "gcp_undistort_u8": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
+    "gcp_undistort_f32": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
 }
 
 ABI_VERSION = 4
 SPLAT_CLAMP_COLOUR, SPLAT_ANTIALIAS = 1, 2  # GCP_SPLAT_* of the header
 METRICS_CLAMP = 1  # GCP_METRICS_CLAMP
+LENS_WORDS, LENS_KINDS = 20, ("pinhole", "polynomial", "fisheye")  # GCP_LENS_WORDS; GCP_LENS_* = the index of the kind
 
 _lib = None
 

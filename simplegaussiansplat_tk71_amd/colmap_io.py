@@ -106,13 +106,15 @@ def qvec_to_rotmat(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
-def load_colmap_tensors(directory, device="cpu"):
-    """sparse/0 directory -> [xyz (n,3), P (m,3,4), K (m,3,3), wh (m,2), image names]
-    (reference: gs_load_colmap.py:66-117; lens distortion is ignored there too)."""
+def load_colmap_tensors(directory, device="cpu", lenses=False):
+    """sparse/0 directory -> [xyz (n,3), P (m,3,4), K (m,3,3), wh (m,2), image names] (reference: gs_load_colmap.py:66-117).
+    K holds fx, fy, cx, cy as the file gives them.  lenses=True appends the per-image list of `lens.Lens` — the same
+    intrinsics with the camera model's distortion coefficients —, with which `lens.fit_pinhole` and `lens.undistort` resample
+    the photographs into pinhole cameras; the K to train on is then the fitted one.  The reference reads no distortion."""
     cameras = read_cameras(os.path.join(directory, "cameras.bin"))
     images = read_images(os.path.join(directory, "images.bin"))
     points = read_points3d(os.path.join(directory, "points3D.bin"))
-    P, K, wh, names = [], [], [], []
+    P, K, wh, names, per_image = [], [], [], [], []
     for iid in images:
         im = images[iid]
         cam = cameras[im["camera_id"]]
@@ -125,6 +127,11 @@ def load_colmap_tensors(directory, device="cpu"):
         K.append([[fx, 0, cx], [0, fy, cy], [0, 0, 1]])
         wh.append([cam["width"], cam["height"]])
         names.append(im["name"])
+        if lenses:
+            from .lens import lens_from_colmap
+
+            per_image.append(lens_from_colmap(cam))
     as_t = lambda a, shape: torch.tensor(np.array(a, dtype=np.float32).reshape(shape), device=device)  # noqa: E731
-    return [torch.tensor(points["xyz"], dtype=torch.float32, device=device), as_t(P, (-1, 3, 4)), as_t(K, (-1, 3, 3)),
-            as_t(wh, (-1, 2)), names]
+    out = [torch.tensor(points["xyz"], dtype=torch.float32, device=device), as_t(P, (-1, 3, 4)), as_t(K, (-1, 3, 3)),
+           as_t(wh, (-1, 2)), names]
+    return out + [per_image] if lenses else out

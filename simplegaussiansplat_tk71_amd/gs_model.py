@@ -8,9 +8,9 @@ Row f4 of SURVEY.md §8: this is caller integration, PyTorch on the GPU around t
 This module holds the model and dataset classes and the reference's small helpers.  What the model calls lives next to
 it and is re-exported from here under the names it always had: the camera projection (projection.py: `camera_inputs`),
 the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
-(density.py: `accumulate_screen_grads`) and the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
-`apply_filter`).  Differences from the reference's class, all deliberate (those of the projection:
-projection.py):
+(density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
+`apply_filter`) and the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`).
+Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
   * one Function call per camera, never chunked (nothing of pair-list size exists here; gs_model.py:428);
@@ -29,6 +29,7 @@ from .cuda_kernel import paint as _paint
 from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
 from .exposure import CameraExposure
 from .filter3d import apply_filter, filter_from_rate, sampling_rate
+from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
@@ -42,20 +43,24 @@ __all__ = [
     "GS_model_with_param",
     "HipAdam",
     "ImageMetrics",
+    "Lens",
     "accumulate_screen_grads",
     "allreduce_contribution",
     "apply_exposure",
     "apply_filter",
     "camera_inputs",
     "filter_from_rate",
+    "fit_pinhole",
     "gather_metrics",
     "image_metrics",
+    "lens_from_colmap",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
     "mean_neighbour_distance",
     "sampling_rate",
     "splat_loss",
     "split_cameras",
+    "undistort",
 ]
 
 
