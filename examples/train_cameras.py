@@ -38,6 +38,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --distortion-reg 100 --distortion-from 300
                                                              # from iteration 300 the loss gains 100 * the mean per-pixel depth
                                                              # distortion (Mip-NeRF 360 / 2DGS): pulls each ray's weights together
+    python examples/train_cameras.py --normal-reg 0.05 --normal-from 300
+                                                             # from iteration 300 the loss gains 0.05 * 2DGS's normal consistency:
+                                                             # the blended normals against the normals of the rendered depth
     python examples/train_cameras.py --colmap DIR --exposure --save-exposure exposure.json
                                                              # one learned 3 x 4 colour affine per training photograph, applied
                                                              # to the render inside the loss kernels (upstream 3DGS's exposure
@@ -125,7 +128,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
           screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
-          exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None):
+          exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -181,6 +184,12 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     record then says "exposure": "identity".  `save_exposure`: write the matrices there as one JSON object, image name ->
     3 x 4 list (rank 0).  Scene brightness times exposure gain is not pinned (as upstream) and no regulariser is added.  With
     exposure=False (the default) no step changes.
+    `normal_reg` L > 0: from iteration `normal_from` on, the step renders through `model.render(normals=True)` (over black where
+    no `background` is set) and the loss gains L * `gs_model.normal_consistency(depth, alpha, normal, K)` of this rank's share —
+    2DGS's normal-consistency loss, the blended per-Gaussian normals against the normals of the rendered depth surface, with
+    the K of the cameras the step drew (under --undistort the fitted cameras').  2DGS trains with L = 0.05 from iteration 7000;
+    that is a pointer, not a tuned value: no full-length run on real poses exists here.  With L = 0 (the default) no step
+    changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -268,8 +277,9 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             mine = idx[rank::world]
             if mine.numel():
                 distort = distortion_reg > 0 and iteration >= distortion_from
-                dist = None
-                if background is None and not distort:
+                with_normals = normal_reg > 0 and iteration >= normal_from
+                dist = nmaps = None
+                if background is None and not distort and not with_normals:
                     images, kept, grad_iter = model(P[mine], K[mine], wh[mine], mine.tolist())
                     target = targets[torch.tensor(kept, device=dev)]
                 else:
@@ -278,9 +288,11 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                         bg = torch.rand(3, device=dev) if isinstance(background, str) else torch.as_tensor(background, dtype=torch.float32,
                                                                                                               device=dev)
                     images, *maps, kept, grad_iter = model.render(P[mine], K[mine], wh[mine], background=bg, image_sample=mine.tolist(),
-                                                                  distortion=distort)
+                                                                  distortion=distort, **({"normals": True} if with_normals else {}))
                     dist = maps[2] if distort else None
                     sel = torch.tensor(kept, device=dev)
+                    if with_normals:
+                        nmaps = (maps[0], maps[1], maps[-1], K[sel])
                     target = targets[sel]
                     if bg is not None and target_alpha is not None:
                         target = target + (1 - target_alpha[sel]) * bg[None, :, None, None]
@@ -290,6 +302,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                     loss = gm.splat_loss(images, target, loss_lamda, exposure=ce.rows(kept)) * (mine.numel() / idx.numel())
                 if dist is not None:  # the geometric regulariser: the mean per-pixel depth distortion of this rank's share
                     loss = loss + distortion_reg * dist.mean() * (mine.numel() / idx.numel())
+                if nmaps is not None:  # the blended normals against the normals of the rendered depth surface
+                    loss = loss + normal_reg * gm.normal_consistency(*nmaps) * (mine.numel() / idx.numel())
                 if densify == "mcmc":  # the regularisers that let opacities die and keep scales small; the whole term on every rank's share
                     loss = loss + (opacity_reg * torch.sigmoid(model.opacity).mean()
                                    + scale_reg * torch.exp(model.variance_scale).mean()) * (mine.numel() / idx.numel())
@@ -427,6 +441,11 @@ def build_parser():
     ap.add_argument("--distortion-reg", type=float, default=0.0, metavar="L",
                     help="weight of the mean per-pixel depth distortion (Mip-NeRF 360 / 2DGS) in the loss (0: off; not tuned here)")
     ap.add_argument("--distortion-from", type=int, default=0, metavar="I", help="with --distortion-reg: the first iteration that carries the term")
+    ap.add_argument("--normal-reg", type=float, default=0.0, metavar="L",
+                    help="weight of 2DGS's normal-consistency loss, the blended normals against the normals of the rendered depth "
+                         "(0: off; 2DGS uses 0.05; not tuned here)")
+    ap.add_argument("--normal-from", type=int, default=7000, metavar="I",
+                    help="with --normal-reg: the first iteration that carries the term (7000 is 2DGS's; not tuned here)")
     ap.add_argument("--filter-3d", action="store_true",
                     help="Mip-Splatting's 3-D smoothing filter: every Gaussian low-pass filtered in world space by the highest rate a training "
                          "camera samples it at, its mass kept; full Mip-Splatting is --filter-3d --centres subpixel --dilation 0.1 --antialias")
@@ -481,7 +500,8 @@ if __name__ == "__main__":
                       test_every=a.test_every, eval_every=a.eval_every, evals=evals, names=names,
                       screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from,
                       filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
-                      exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure)
+                      exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure, normal_reg=a.normal_reg,
+                      normal_from=a.normal_from)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

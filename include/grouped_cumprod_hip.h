@@ -1004,6 +1004,47 @@ int gcp_undistort_u8(const uint8_t* src, const float* lenses, int64_t images, in
 int gcp_undistort_f32(const float* src, const float* lenses, int64_t images, int32_t height, int32_t width, float* dst,
                       void* stream);
 
+/* ---- normals: per-Gaussian normals and 2DGS's depth-normal consistency loss (csrc/gcp_normal.hip) -----------------------
+ * gcp_normals_forward: for list entry j of one camera, i = index[j] (int64, no repeats; an entry outside [0, n_gauss) gets a
+ *   zero normal and no gradient):  q^ = variance_q[i] / max(|q|, 1e-8) (xyzw, the projection's normalisation),
+ *   k = argmin_a variance_scale[i][a] (the raw log scale; ties to the lowest a),  n_w = column k of R(q^),
+ *   n_c = P[:, :3] n_w,  t_c = P[:, :3] mean[i] + P[:, 3]  (P f32[3][4] world->camera, its left block a rotation),
+ *   normal[j] = n_c if n_c . t_c <= 0, else -n_c: the normal faces the camera.  aux[j] = k | (4 if negated), for the backward.
+ * gcp_normals_backward: g_normal f32[n_list][3] -> g_q f32[n_gauss][4], through the column of R and the normalisation
+ *   (the axis choice and the flip are piecewise constant: variance_scale and mean get no gradient).  Every row is written:
+ *   the rows absent from the list are exact zeros (one memset node, then the kernel).
+ * One thread per list entry, no grid cap, no atomics, no device->host read (capturable); the same bits whatever the launch
+ * shape.  n_list may equal n_gauss (capture-safe lists, which keep the culled entries).  n_list == 0 is a no-op for the
+ * forward; the backward still clears g_q.  GCP_ERR_INVALID_ARGUMENT: a negative count, one above INT32_MAX, a NULL pointer.
+ *
+ * gcp_normal_consistency_forward / _backward: depth D, alpha A f32[images][height][width], normal N f32[images][3][height][width],
+ * K f32[images][3][3] ON THE DEVICE.  Per image and pixel p = (x, y):
+ *   valid(p) = A(p) >= alpha_min and D(p) > 0;   z = D / A;   r(p) = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1);   pt = z r;
+ *   defined(p): p and (x +- 1, y), (x, y +- 1) are inside the frame and valid;
+ *   c = (pt(x, y+1) - pt(x, y-1)) x (pt(x+1, y) - pt(x-1, y)),  n~ = c / |c|  (a fronto-parallel surface: (0, 0, -1));
+ *   |c| > 0 where defined, since c . r = -(z(x+1,y) + z(x-1,y)) (z(x,y+1) + z(x,y-1)) / (fx fy);
+ *   e(p) = 1 - a(p) N(p) . n~(p) where defined, a = A(p) held constant;  e(p) = 1 elsewhere.
+ * forward: partial f32[gcp_normal_consistency_blocks(images, height, width)] receives one sum of e per 32 x 16 tile, image
+ *   by image, tiles row-major — the caller adds them (in float64, in a fixed order) and divides by images * height * width;
+ *   e_map f32[images][height][width] and depth_normal f32[images][3][height][width] (n~, 0 where not defined): NULL = not written.
+ * backward: scale f32[1] on the device = dLoss / d(sum of e);  g_normal = -scale a n~ where defined;  g_depth, g_alpha through
+ *   z of the four neighbours (none through the factor a), gathered per pixel from the up to four defined stencils that contain
+ *   it; every word of the three outputs is written (0 where nothing reaches it).  Nothing is saved by the forward.
+ * One launch per direction, no atomics, no workspace, no device->host read; an image's numbers depend on that image alone.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: images < 0, height or width < 1, height * width > INT32_MAX, alpha_min not
+ * > 0, more than INT32_MAX tiles, a NULL required pointer.  images == 0 is a no-op. */
+int gcp_normals_forward(const float* variance_q, const float* variance_scale, const float* mean, const float* P, const int64_t* index,
+                        int64_t n_gauss, int64_t n_list, float* normal, uint8_t* aux, void* stream);
+int gcp_normals_backward(const float* variance_q, const float* P, const int64_t* index, const uint8_t* aux, const float* g_normal,
+                         int64_t n_gauss, int64_t n_list, float* g_q, void* stream);
+int64_t gcp_normal_consistency_blocks(int64_t images, int32_t height, int32_t width);
+int gcp_normal_consistency_forward(const float* depth, const float* alpha, const float* normal, const float* K, int64_t images,
+                                   int32_t height, int32_t width, float alpha_min, float* e_map, float* depth_normal, float* partial,
+                                   void* stream);
+int gcp_normal_consistency_backward(const float* depth, const float* alpha, const float* normal, const float* K, int64_t images,
+                                    int32_t height, int32_t width, float alpha_min, const float* scale, float* g_depth, float* g_alpha,
+                                    float* g_normal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

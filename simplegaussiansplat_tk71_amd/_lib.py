@@ -171,6 +171,14 @@ SIGNATURES = {
     # dst f32[n,3,H,W], stream
     "gcp_undistort_u8": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
     "gcp_undistort_f32": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p]),
+    # normals (gcp_normal.hip): per-Gaussian normals (q, log scale, mean, P, index, n, m -> normal, aux; its backward: q, P, index,
+    # aux, g_normal, n, m -> g_q) and the depth-normal consistency loss (depth, alpha, normal, K, images, height, width, alpha_min
+    # -> e_map or NULL, depth_normal or NULL, partial; its backward: ... alpha_min, scale -> g_depth, g_alpha, g_normal); stream last
+    "gcp_normals_forward": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i64] + [_c_void_p] * 3),
+    "gcp_normals_backward": (ctypes.c_int, [_c_void_p] * 5 + [_i64, _i64] + [_c_void_p] * 2),
+    "gcp_normal_consistency_blocks": (_i64, [_i64, _i32, _i32]),
+    "gcp_normal_consistency_forward": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i32, _i32, ctypes.c_float] + [_c_void_p] * 4),
+    "gcp_normal_consistency_backward": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i32, _i32, ctypes.c_float] + [_c_void_p] * 5),
 }
 
 ABI_VERSION = 4

@@ -65,6 +65,7 @@ __all__ = [
     "custom_autograd_grouped_cumprod",
     "RenderDepth",
     "RenderDistortion",
+    "RenderNormal",
     "render",
     "contribution",
     "absgrad_buffer",
@@ -762,8 +763,69 @@ class RenderDistortion(torch.autograd.Function):
                 g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
 
 
+class RenderNormal(torch.autograd.Function):
+    """`RenderDepth` (distortion False) or `RenderDistortion` (True) with one more output, last: the normal map
+    nmap (H+1, W+1, 3) = sum_k w_k n_k of per-Gaussian normals `normal` [N, 3]; see `render(normal=)`.  The map is painted by
+    the colour blend (k_blend_fwd, normals in place of l_d) on the bins of the image — one binning per camera — and its
+    gradient is a second `blend_backward` on the image's transmittance checkpoints, whose g_mean, g_vinv and g_op are added
+    to those of the other maps (the backward is linear in the upstream gradients).  The other maps come from the same kernels
+    as without `normal`: the same bits; when the loss does not use nmap its gradient arrives as None, nothing extra is
+    launched and the gradients are those of the call without `normal` bit for bit.  Capture-safe and overflow-reporting like
+    the other Functions; the optional trailing `absgrad` buffer is filled from the gradients of the THREE maps only."""
+
+    @staticmethod
+    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                normal, distortion, *absgrad):
+        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background, normal)
+        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
+        ctx.distortion = bool(distortion)
+        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
+        with torch.no_grad():
+            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                     l_d, depth, background, with_checkpoints=True)
+            extra, saved = (), ()
+            if ctx.distortion:
+                dist, a_n, b_n = _raster.blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
+                extra, saved = (dist,), (a_n, b_n)
+            nmap = _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, normal)
+        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *saved)
+        return (image, dmap, alpha, *extra, nmap)
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_alpha, *g_rest):
+        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *saved), bins = _saved_with_bins(ctx)
+        g_dist, g_nmap = (g_rest[0] if ctx.distortion else None), g_rest[-1]
+        want_bg = background is not None and ctx.needs_input_grad[9]
+        g_normal = None
+        with torch.no_grad():
+            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
+                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
+                background, background_grad=want_bg)
+            if ctx.absgrad is not None:
+                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
+                                            g_depth, g_alpha, background, out=ctx.absgrad)
+            if g_dist is not None:
+                a_n, b_n = saved
+                d_mean, d_vinv, d_op, d_z = _raster.blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                           depth, t_ckpt, a_n, b_n, g_dist)
+                g_mean += d_mean
+                g_vinv += d_vinv
+                g_op += d_op
+                g_z += d_z
+            if g_nmap is not None:
+                n_mean, n_vinv, n_op, g_normal = _raster.blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                        normal, t_ckpt, g_nmap)
+                g_mean += n_mean
+                g_vinv += n_vinv
+                g_op += n_op
+        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
+        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
+                g_bg.reshape(background.shape) if want_bg else None, g_normal, None) + (None,) * ctx.n_absgrad
+
+
 def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None,
-           distortion=False):
+           distortion=False, normal=None):
     """Rasterise and blend one camera's depth-ordered Gaussians (the arguments of `custom_autograd_grouped_cumprod`, without
     boxsize / batch) -> (image (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), differentiable in mean (if float),
     variance_inverse, opacity, l_d, depth and background.
@@ -788,7 +850,20 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
     order — as the camera depth the list is sorted by is; ties contribute 0.  Like the depth map it is not divided by alpha and
     is in units of z.  A loss that does not use `dist` launches no distortion kernel in backward and gets the gradients of the
     three-map call bit for bit.  With `absgrad` given the buffer is filled from the three maps' gradients only: the
-    regulariser's term is not part of the densification statistic."""
+    regulariser's term is not part of the densification statistic.
+    `normal`: None, or a float32 [N, 3] device tensor of per-Gaussian normals in list order (`normals.gaussian_normals`)
+    (`RenderNormal`) -> one more map, last: nmap (H+1, W+1, 3) = sum_k w_k n_k with the pair rule and the weights of the image —
+    NOT divided by alpha, no background — painted by the colour blend on the same bins, differentiable in `normal` and, through
+    the weights, in mean (if float), variance_inverse and opacity.  The other maps are the same bits with and without it, it
+    combines with `distortion=True` ((image, depth, alpha, dist, nmap)), a loss that does not use nmap launches nothing extra in
+    backward and gets the other call's gradients bit for bit, and `absgrad` is filled from the three maps' gradients only."""
+    if normal is not None:
+        n = startpoint.shape[0]
+        if not (isinstance(normal, torch.Tensor) and tuple(normal.shape) == (n, 3) and normal.device == startpoint.device):
+            raise RuntimeError(f"normal: expected an [{n}, 3] tensor on {startpoint.device} (normals.gaussian_normals), or None")
+        extra = () if absgrad is None else (absgrad,)
+        return RenderNormal.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                                  normal, bool(distortion), *extra)
     fn = RenderDistortion if distortion else RenderDepth
     if absgrad is None:
         return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)

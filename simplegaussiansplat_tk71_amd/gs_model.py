@@ -9,7 +9,8 @@ This module holds the model and dataset classes and the reference's small helper
 it and is re-exported from here under the names it always had: the camera projection (projection.py: `camera_inputs`),
 the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
 (density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
-`apply_filter`) and the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`).
+`apply_filter`), the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`) and the
+normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`).
 Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
@@ -31,6 +32,7 @@ from .exposure import CameraExposure
 from .filter3d import apply_filter, filter_from_rate, sampling_rate
 from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
+from .normals import depth_normals, gaussian_normals, normal_consistency, normal_consistency_map
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
@@ -49,14 +51,18 @@ __all__ = [
     "apply_exposure",
     "apply_filter",
     "camera_inputs",
+    "depth_normals",
     "filter_from_rate",
     "fit_pinhole",
     "gather_metrics",
+    "gaussian_normals",
     "image_metrics",
     "lens_from_colmap",
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
     "mean_neighbour_distance",
+    "normal_consistency",
+    "normal_consistency_map",
     "sampling_rate",
     "splat_loss",
     "split_cameras",
@@ -704,7 +710,7 @@ class GS_model_with_param(torch.nn.Module):
         out = out.reshape(-1, 3, h, w) if self.reference_layout else out.permute(0, 3, 1, 2).contiguous()
         return [out, names, grad_iter]
 
-    def render(self, P, K, wh, background=None, image_sample=None, distortion=False):
+    def render(self, P, K, wh, background=None, image_sample=None, distortion=False, normals=False):
         """`forward` with the expected-depth and alpha maps and a background colour (`cuda_kernel.render`, whose
         docstring pins the definitions: depth = sum of the colour weights times the camera-space depth, NOT divided by
         alpha; alpha = 1 - the transmittance behind the pixel; image composited over `background`, a float[3] device tensor
@@ -714,15 +720,29 @@ class GS_model_with_param(torch.nn.Module):
         distortion=True: [images, depth, alpha, distortion (B, 1, H, W), names, grad_iter] — the per-pixel depth distortion
         of `cuda_kernel.render(distortion=True)` (sum_{i>j} 2 w_i w_j (z_i - z_j) over the pixel's kept pairs, z the
         camera-space depth the list is sorted by; not divided by alpha), cropped like the others; the first three maps are the
-        same bits as without it."""
+        same bits as without it.
+        normals=True: one more map after those, normal (B, 3, H, W) = sum_k w_k n_k in camera coordinates, cropped like the
+        others, not divided by alpha — [images, depth, alpha, (distortion,) normal, names, grad_iter].  Per camera the
+        normals of its list come from `gaussian_normals` on the RAW parameters (variance_q, variance_scale, mean; the 3-D
+        filter does not change which axis is the shortest) and `cam["index"]`, and are blended by
+        `cuda_kernel.render(normal=)`; their gradient reaches variance_q, the map's weights' the other parameters.  What
+        `normal_consistency(depth, alpha, normal, K)` takes.  The other maps are the same bits as without it."""
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
         self._watch_centres(cams, width, height)
+        if normals:
+            for c, cam in enumerate(cams):
+                if cam is not None:
+                    cam["normal"] = gaussian_normals(self.variance_q, self.variance_scale, self.mean, P[c], cam["index"])
         maps, names = self._draw_cameras(
             cams, range(P.shape[0]) if image_sample is None else image_sample,
             lambda cam: render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
-                               cam["depth"], width, height, background, cam.get("absgrad"), distortion=distortion))
+                               cam["depth"], width, height, background, cam.get("absgrad"), distortion=distortion,
+                               normal=cam.get("normal")))
         images = maps[0][:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
-        planes = [m[:, None, 1:, 1:].contiguous() for m in maps[1:]]  # depth, alpha[, distortion]
+        n_planes = len(maps) - (2 if normals else 1)
+        planes = [m[:, None, 1:, 1:].contiguous() for m in maps[1:1 + n_planes]]  # depth, alpha[, distortion]
+        if normals:
+            planes.append(maps[-1][:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous())
         return [images, *planes, names, grad_iter]
 
     @torch.no_grad()
