@@ -128,7 +128,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           densify="reference", densify_on="position", antialias=False, cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01,
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
           screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
-          exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000):
+          exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000, save_mesh=None, mesh_resolution=256,
+          mesh_trunc=None):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -190,6 +191,11 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     the K of the cameras the step drew (under --undistort the fitted cameras').  2DGS trains with L = 0.05 from iteration 7000;
     that is a pointer, not a tuned value: no full-length run on real poses exists here.  With L = 0 (the default) no step
     changes.
+    `save_mesh`: after the last step rank 0 fuses the depth maps of the TRAINING cameras into a TSDF volume and writes its zero
+    level set there as a triangle mesh (`model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc)`,
+    `ply_io.save_mesh`; `batch_size` cameras at a time; a running mean is order-dependent, so the ranks do not share the work).
+    `mesh_resolution` = 256 and the default truncation of 5 voxels are pointers from 2DGS's usage, not tuned here.  With
+    save_mesh=None (the default) no step and no output changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -381,6 +387,12 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         model.save_ply(save_ply)
     if ce is not None and save_exposure is not None and rank == 0:
         ce.save_json(save_exposure)
+    if save_mesh is not None and rank == 0:
+        from simplegaussiansplat_tk71_amd import ply_io
+
+        vertices, faces, colours = model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc, batch_size=batch_size)
+        ply_io.save_mesh(save_mesh, vertices, faces, colours)
+        log(f"mesh: {vertices.shape[0]} vertices, {faces.shape[0]} faces -> {save_mesh}")
     return model, losses
 
 
@@ -458,6 +470,13 @@ def build_parser():
     ap.add_argument("--exposure-lr-init", type=float, default=0.01, help="with --exposure: the first learning rate (upstream's, not tuned here)")
     ap.add_argument("--exposure-lr-final", type=float, default=0.001, help="with --exposure: the rate after 30 000 steps (upstream's)")
     ap.add_argument("--save-exposure", default=None, metavar="PATH", help="with --exposure: write the matrices as JSON, image name -> 3 x 4 list")
+    ap.add_argument("--save-mesh", default=None, metavar="PATH",
+                    help="after the last step: fuse the training cameras' depth maps into a TSDF volume and write its surface as a "
+                         "triangle mesh .ply (rank 0); what --normal-reg and --distortion-reg shape the depth for")
+    ap.add_argument("--mesh-resolution", type=int, default=256, metavar="N",
+                    help="with --save-mesh: voxels along the scene cube's side (256: a pointer from 2DGS's usage, not tuned here)")
+    ap.add_argument("--mesh-trunc", type=float, default=None, metavar="F",
+                    help="with --save-mesh: the truncation distance in world units (default: 5 voxels; not tuned here)")
     return ap
 
 
@@ -501,7 +520,7 @@ if __name__ == "__main__":
                       screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from,
                       filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
                       exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure, normal_reg=a.normal_reg,
-                      normal_from=a.normal_from)
+                      normal_from=a.normal_from, save_mesh=a.save_mesh, mesh_resolution=a.mesh_resolution, mesh_trunc=a.mesh_trunc)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -1045,6 +1045,57 @@ int gcp_normal_consistency_backward(const float* depth, const float* alpha, cons
                                     int32_t height, int32_t width, float alpha_min, const float* scale, float* g_depth, float* g_alpha,
                                     float* g_normal, void* stream);
 
+/* ---- mesh extraction: TSDF fusion of depth maps, marching tetrahedra (csrc/gcp_tsdf.hip) --------------------------------
+ * The volume: nz x ny x nx lattice points, x fastest; point (i, j, k) sits at origin + voxel (i, j, k) in world coordinates.
+ * State, float32 planes of that layout on the device: tsdf, weight, and optionally rgb f32[3][nz][ny][nx].  A fresh volume has
+ * tsdf = 1, weight = 0, rgb = 0 (the caller fills them).
+ *
+ * gcp_tsdf_integrate: one launch integrates `cameras` cameras.  depth, alpha f32[cameras][height][width] as the blend paints
+ * them (depth NOT divided by alpha), image f32[cameras][3][height][width] (read only with rgb), P f32[cameras][3][4]
+ * world->camera, K f32[cameras][3][3], all ON THE DEVICE.  For a lattice point x_w, for c = 0 .. cameras - 1 in that order:
+ *   p = R_c x_w + t_c;  z = p.z;                          skip unless z > 0
+ *   u = fx p.x / z + cx;  v = fy p.y / z + cy             (pixel centres at +0.5 in K's coordinates)
+ *   skip unless 0 <= u < width and 0 <= v < height        (compared in float before any conversion);  x = floor u, y = floor v
+ *   a = alpha[c][y][x], D = depth[c][y][x];               skip unless a >= alpha_min and D > 0   (a NaN skips)
+ *   d = D / a;                                            skip if depth_max > 0 and d > depth_max
+ *   s = d - z;                                            skip if s < -trunc
+ *   tau = min(1, s / trunc);  tsdf <- (tsdf w + tau) / (w + 1);  rgb likewise with image[c][:][y][x];  w <- w + 1
+ * Open3D's projective z-depth TSDF with nearest-pixel lookup and unit weights.  One thread per lattice point, the state in
+ * registers over the camera loop, float32 throughout: cameras 0 .. B-1 in one launch, one at a time or in any split give the
+ * same bits.  No atomics, no workspace, no device->host read (capturable).
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: a dimension < 2, nx ny nz >= 2^31, voxel or trunc not > 0 or not finite, a
+ * non-finite origin, cameras < 0, and with cameras > 0: height or width < 1, height * width > INT32_MAX, a NULL tsdf, weight,
+ * depth, alpha, P or K, rgb without image.  cameras == 0 is a no-op.
+ *
+ * gcp_mesh_count / gcp_mesh_write: the level set tsdf = iso as an indexed triangle mesh, by marching tetrahedra.  A cell is the
+ * cube between (i, j, k) and (i+1, j+1, k+1); it is VALID when all 8 corners have weight > 0 (weight NULL: every cell).  A
+ * cell is cut into the 6 Kuhn tetrahedra {c, c + e_a, c + e_a + e_b, c + (1,1,1)}, (a, b) = (x,y) (x,z) (y,x) (y,z) (z,x) (z,y)
+ * in that order.  A corner is inside when f < iso.  Vertices live on lattice edges of 7 kinds from their lower end point, which
+ * owns them: +x, +y, +z, +xy, +xz, +yz, +xyz.  An edge carries one vertex when its end points differ in side, both lie in the
+ * grid and at least one valid cell contains it: at x_p + t (x_q - x_p), t = (iso - f_p) / (f_q - f_p), p the owner; colours are
+ * interpolated the same way.  A tetrahedron with 1 or 3 inside corners gives 1 triangle, with 2 gives 2 (the quadrilateral
+ * (a o0, a o1, b o1, b o0) split along its first and third vertex; a, b inside, o0, o1 outside, in corner order); counter-
+ * clockwise seen from where f grows.  Zero-area triangles (t rounded to 0 or 1) are kept.  Vertices are ordered by (owner, kind),
+ * faces by (cell, tetrahedron, triangle): the same bits on every run.  No unreferenced and no duplicated vertex.
+ *   gcp_mesh_count fills ws (gcp_mesh_workspace_bytes(nx, ny, nz) bytes, 256-byte aligned) and writes the number of vertices
+ *     and of faces to totals_host[0..1] — it synchronises the stream once for that read: NOT capturable.
+ *     GCP_ERR_INVALID_ARGUMENT as well when 3 V or 3 F does not fit int32.
+ *   gcp_mesh_write takes the same tsdf, dimensions, iso and the ws gcp_mesh_count filled, and writes vertices f32[V][3],
+ *     faces int32[F][3] and, with rgb and colours given, colours f32[V][3].  V = 0 and F = 0 launch nothing.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: a dimension < 2, nx ny nz >= 2^31, voxel not > 0, a NaN iso, a NULL tsdf, ws or
+ * totals_host, negative totals, NULL outputs with work to do, colours without rgb; GCP_ERR_WORKSPACE: ws too small or
+ * misaligned.  gcp_mesh_workspace_bytes returns 0 for refused dimensions. */
+int gcp_tsdf_integrate(float* tsdf, float* weight, float* rgb, int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y,
+                       float origin_z, float voxel, float trunc, const float* depth, const float* alpha, const float* image,
+                       const float* P, const float* K, int64_t cameras, int32_t height, int32_t width, float alpha_min,
+                       float depth_max, void* stream);
+size_t gcp_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int gcp_mesh_count(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float iso, void* ws, size_t ws_bytes,
+                   int64_t* totals_host, void* stream);
+int gcp_mesh_write(const float* tsdf, const float* rgb, int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z,
+                   float voxel, float iso, const void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_faces, float* vertices,
+                   int32_t* faces, float* colours, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,16 @@ SIGNATURES = {
     "gcp_normal_consistency_blocks": (_i64, [_i64, _i32, _i32]),
     "gcp_normal_consistency_forward": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i32, _i32, ctypes.c_float] + [_c_void_p] * 4),
     "gcp_normal_consistency_backward": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i32, _i32, ctypes.c_float] + [_c_void_p] * 5),
+    # mesh extraction (gcp_tsdf.hip): TSDF integration (tsdf, weight, rgb or NULL, nx, ny, nz, origin x y z, voxel, trunc, depth,
+    # alpha, image or NULL, P, K, cameras, height, width, alpha_min, depth_max, stream) and marching tetrahedra: count (tsdf,
+    # weight or NULL, nx, ny, nz, iso, ws, ws_bytes -> host int64[2] vertices, faces) and write (tsdf, rgb or NULL, nx, ny, nz,
+    # origin x y z, voxel, iso, ws, ws_bytes, vertices, faces -> vertices, faces, colours or NULL); stream last
+    "gcp_tsdf_integrate": (ctypes.c_int, [_c_void_p] * 3 + [_i32] * 3 + [ctypes.c_float] * 5 + [_c_void_p] * 5 + [_i64, _i32, _i32]
+                           + [ctypes.c_float] * 2 + [_c_void_p]),
+    "gcp_mesh_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "gcp_mesh_count": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32, ctypes.c_float, _c_void_p, _sz, ctypes.POINTER(_i64), _c_void_p]),
+    "gcp_mesh_write": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32] + [ctypes.c_float] * 5 + [_c_void_p, _sz, _i64, _i64]
+                       + [_c_void_p] * 4),
 }
 
 ABI_VERSION = 4

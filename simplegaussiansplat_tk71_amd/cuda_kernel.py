@@ -70,6 +70,7 @@ __all__ = [
     "contribution",
     "absgrad_buffer",
     "paint",
+    "paint_maps",
     "tile_capacity",
     "capacity_exceeded",
     "GraphedStep",
@@ -894,3 +895,14 @@ def paint(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_widt
             return _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False)
         return _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
                                            with_checkpoints=False)[0]
+
+
+def paint_maps(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth, background=None):
+    """What `paint` does with `depth` [N] given, but all three maps `render` paints from the same arguments -> (image
+    (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), detached: bins, then `raster.blend_forward_depth` WITHOUT transmittance
+    checkpoints, no autograd node.  The image is `paint(..., depth=depth, background=background)` bit for bit; the depth map is
+    NOT divided by alpha.  What `mesh.TSDFVolume.integrate` fuses (after the [1:, 1:] crop).  GPU tensors only."""
+    with torch.no_grad():
+        bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+        return _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
+                                           with_checkpoints=False)

@@ -10,7 +10,8 @@ it and is re-exported from here under the names it always had: the camera projec
 the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
 (density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
 `apply_filter`), the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`) and the
-normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`).
+normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`) and the mesh extraction
+(mesh.py: `TSDFVolume`, `extract_surface`).
 Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
@@ -27,11 +28,13 @@ from .cuda_kernel import absgrad_buffer as _absgrad_buffer
 from .cuda_kernel import contribution as _camera_contribution
 from .cuda_kernel import custom_autograd_grouped_cumprod, render
 from .cuda_kernel import paint as _paint
+from .cuda_kernel import paint_maps as _paint_maps
 from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
 from .exposure import CameraExposure
 from .filter3d import apply_filter, filter_from_rate, sampling_rate
 from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
+from .mesh import TSDFVolume, extract_surface
 from .normals import depth_normals, gaussian_normals, normal_consistency, normal_consistency_map
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
@@ -46,12 +49,14 @@ __all__ = [
     "HipAdam",
     "ImageMetrics",
     "Lens",
+    "TSDFVolume",
     "accumulate_screen_grads",
     "allreduce_contribution",
     "apply_exposure",
     "apply_filter",
     "camera_inputs",
     "depth_normals",
+    "extract_surface",
     "filter_from_rate",
     "fit_pinhole",
     "gather_metrics",
@@ -788,3 +793,65 @@ class GS_model_with_param(torch.nn.Module):
             empty = torch.zeros(0, dtype=torch.float64, device=self.mean.device)
             return ImageMetrics(empty, empty.clone(), empty.clone(), empty.clone())
         return ImageMetrics(*(torch.cat(field) for field in zip(*parts)))
+
+    # ---- mesh extraction (mesh.py, csrc/gcp_tsdf.hip) ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def extract_mesh(self, P, K, wh, resolution=256, bounds=None, trunc=None, alpha_min=0.5, depth_max=None, batch_size=4, colour=True):
+        """A triangle mesh of the scene -> (vertices float32 (V, 3), faces int32 (F, 3), colours float32 (V, 3) or None): the
+        depth maps of the cameras (P, K, wh) — pass the TRAINING cameras — fused into a truncated signed distance volume
+        (`TSDFVolume.integrate`), its zero level set extracted by marching tetrahedra (`TSDFVolume.extract`); what 2DGS, GOF,
+        RaDe-GS and PGSR do through Open3D, and what `--normal-reg` / `--distortion-reg` shape the depth for.
+        The cameras are projected with the model's own options (the 3-D filter applies if on) and painted over black by
+        `cuda_kernel.paint_maps` with the [1:, 1:] crop of `render`, `batch_size` at a time, and integrated in the order
+        given; a camera that sees nothing is integrated as an empty map, which changes nothing.
+        `bounds`: ((x0, y0, z0), (x1, y1, z1)), the box the volume covers; default: the cube centred at the centroid of the
+        camera centres with half-side r = the largest camera distance from that centroid (2DGS's bounded-scene radius).
+        `resolution`: lattice points along the longest side: voxel = longest side / resolution (2 r / resolution by default), the
+        other sides get as many points as cover them.  `trunc`: the truncation distance, default 5 voxel.  `depth_max`: depths
+        beyond it are not fused, default the longest side (2 r); 0 = no limit.  `alpha_min`: pixels fainter than this are not
+        fused.  resolution = 256, 5 voxels and alpha_min = 0.5 are pointers from 2DGS and Open3D usage; they are not tuned here.
+        colour=False: no colour volume, colours is None.
+        Mean-depth fusion of a bounded scene only: no median depth, no mesh cleaning, no vertex normals.
+        Nothing of the training state is touched: no `.grad`, no densification statistic, no optimiser state, no generator —
+        like `evaluate`.  The host reads are those of the projection and the binning, and one for the mesh's size.  GPU only."""
+        n_cam, dev = P.shape[0], self.mean.device
+        if not self.mean.is_cuda:
+            raise RuntimeError("extract_mesh runs HIP kernels: the model must live on the GPU (no CPU path)")
+        resolution = int(resolution)
+        if resolution < 2:
+            raise RuntimeError("resolution: at least 2")
+        if bounds is None:
+            if n_cam == 0:
+                raise RuntimeError("extract_mesh: no camera and no bounds")
+            Pd = P.detach().to(device=dev, dtype=torch.float64)
+            centres = -(Pd[:, :, :3] * Pd[:, :, 3:]).sum(dim=1)  # -R^T t, camera by camera
+            centroid = centres.mean(dim=0)
+            r = float((centres - centroid).norm(dim=1).max())
+            lo, hi = [float(c) - r for c in centroid], [float(c) + r for c in centroid]
+        else:
+            lo, hi = [float(v) for v in bounds[0]], [float(v) for v in bounds[1]]
+        sides = [h - l for l, h in zip(lo, hi)]
+        if len(sides) != 3 or not min(sides) > 0.0:
+            raise RuntimeError(f"bounds: a box with three positive sides expected, got {lo} .. {hi}")
+        voxel = max(sides) / resolution
+        dims = tuple(max(2, int(math.ceil(side / voxel - 1e-9)) + 1) for side in sides)
+        trunc = 5.0 * voxel if trunc is None else float(trunc)
+        depth_max = max(sides) if depth_max is None else float(depth_max)
+        volume = TSDFVolume(lo, voxel, dims, trunc, dev, colour=colour)
+        batch_size = max(1, int(batch_size))
+        for c in range(0, n_cam, batch_size):
+            Pb, Kb = P[c:c + batch_size], K[c:c + batch_size]
+            cams, _, (width, height) = self.camera_inputs(Pb, Kb, wh[c:c + batch_size], with_depth=True)
+            frames = []
+            for cam in cams:
+                if cam is None:  # nothing in view: alpha = 0 everywhere, no lattice point is updated
+                    frames.append((torch.zeros(height + 1, width + 1, 3, dtype=torch.float32, device=dev),
+                                   torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev),
+                                   torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev)))
+                else:
+                    frames.append(_paint_maps(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
+                                              cam["l_d"], width, height, cam["depth"]))
+            image, depth, alpha = (torch.stack(maps, dim=0) for maps in zip(*frames))
+            volume.integrate(depth[:, None, 1:, 1:], alpha[:, None, 1:, 1:], Pb.to(dev), Kb.to(dev),
+                             image=image[:, 1:, 1:, :].permute(0, 3, 1, 2) if colour else None, alpha_min=alpha_min, depth_max=depth_max)
+        return volume.extract()

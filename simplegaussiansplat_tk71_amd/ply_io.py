@@ -18,7 +18,7 @@ dependence means the same elsewhere (GS_model_with_param.save_ply warns otherwis
 import numpy as np
 import torch
 
-__all__ = ["save_ply", "load_ply", "property_names"]
+__all__ = ["save_ply", "load_ply", "property_names", "save_mesh", "load_mesh"]
 
 SH_C0 = 0.28209479177387814
 CONVENTIONS = ("3dgs", "raw")
@@ -133,3 +133,77 @@ def load_ply(path, device="cpu", convention="3dgs"):
     out = (take(["x", "y", "z"]), take(["rot_1", "rot_2", "rot_3", "rot_0"]), take([f"scale_{i}" for i in range(3)]),
            take(["opacity"]), color)
     return tuple(torch.from_numpy(a).to(device) for a in out)
+
+
+# ---- triangle meshes (mesh.py) -------------------------------------------------------------------------------------------------
+def _mesh_header(n_vert, n_face, coloured):
+    return ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {n_vert}\n" + "property float x\nproperty float y\nproperty float z\n"
+            + ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if coloured else "")
+            + f"element face {n_face}\n" + "property list uchar int vertex_indices\nend_header\n")
+
+
+def _mesh_dtypes(coloured):
+    vertex = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else [])
+    return np.dtype(vertex), np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def save_mesh(path, vertices, faces, colours=None):
+    """Write an indexed triangle mesh (mesh.extract_surface's outputs) as a binary little-endian .ply that MeshLab, Blender and
+    Open3D read: vertex `x y z` float, plus `red green blue` uchar when `colours` (V, 3) in [0, 1] is given (clamped, scaled by
+    255 and rounded); face `property list uchar int vertex_indices`, three indices each.  vertices (V, 3), faces (F, 3) with
+    indices in [0, V); tensors or arrays; V = 0 or F = 0 is a valid (empty) file."""
+    as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)  # noqa: E731
+    v, f = as_np(vertices), as_np(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"vertices (V, 3) and faces (F, 3) expected, got {v.shape} and {f.shape}")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("faces: an index outside [0, V)")
+    vertex_t, face_t = _mesh_dtypes(colours is not None)
+    rows = np.zeros(v.shape[0], dtype=vertex_t)
+    rows["x"], rows["y"], rows["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colours is not None:
+        c = as_np(colours)
+        if c.shape != v.shape:
+            raise ValueError(f"colours: {v.shape} expected, got {c.shape}")
+        c8 = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        rows["red"], rows["green"], rows["blue"] = c8[:, 0], c8[:, 1], c8[:, 2]
+    tris = np.zeros(f.shape[0], dtype=face_t)
+    tris["n"], tris["v"] = 3, f
+    with open(path, "wb") as out:
+        out.write(_mesh_header(v.shape[0], f.shape[0], colours is not None).encode("ascii"))
+        out.write(rows.tobytes())
+        out.write(tris.tobytes())
+
+
+def load_mesh(path, device="cpu"):
+    """-> (vertices float32 (V, 3), faces int32 (F, 3), colours float32 (V, 3) in [0, 1] or None) on `device`: the inverse of
+    save_mesh (colours come back as multiples of 1 / 255).  Reads the layout save_mesh writes and nothing else."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise ValueError("not a .ply file")
+    header, body = data[:end + 11].decode("ascii", errors="replace"), data[end + 11:]
+    lines = [ln.split() for ln in header.splitlines() if ln and not ln.startswith(("comment", "obj_info"))]
+    elements = [(ln[1], int(ln[2])) for ln in lines if ln[0] == "element" and len(ln) == 3]
+    if [e[0] for e in elements] != ["vertex", "face"]:
+        raise ValueError("a vertex element followed by a face element expected")
+    (_, n_vert), (_, n_face) = elements
+    for coloured in (False, True):
+        if header == _mesh_header(n_vert, n_face, coloured):
+            break
+    else:
+        raise ValueError(f"{path}: not the mesh layout save_mesh writes (binary little-endian; x y z float [red green blue uchar]; "
+                         "list uchar int vertex_indices)")
+    vertex_t, face_t = _mesh_dtypes(coloured)
+    if len(body) != n_vert * vertex_t.itemsize + n_face * face_t.itemsize:
+        raise ValueError(f"{path}: {n_vert} vertices and {n_face} faces expected, the file's length does not match")
+    rows = np.frombuffer(body, dtype=vertex_t, count=n_vert)
+    tris = np.frombuffer(body, dtype=face_t, count=n_face, offset=n_vert * vertex_t.itemsize)
+    if n_face and not (tris["n"] == 3).all():
+        raise ValueError("only triangles are supported")
+    v = np.stack([rows["x"], rows["y"], rows["z"]], axis=1).astype(np.float32)
+    c = np.stack([rows["red"], rows["green"], rows["blue"]], axis=1).astype(np.float32) / np.float32(255.0) if coloured else None
+    faces = np.zeros((n_face, 3), dtype=np.int32)
+    faces[:] = tris["v"]
+    return (torch.from_numpy(v).to(device), torch.from_numpy(faces).to(device), None if c is None else torch.from_numpy(c).to(device))
