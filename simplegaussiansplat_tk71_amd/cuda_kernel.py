@@ -683,39 +683,78 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
         return (None, None, None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, None, None) + (None,) * ctx.n_absgrad
 
 
+def _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, normal,
+                    distortion, absgrad):
+    """The forward of `RenderDepth`, `RenderDistortion` and `RenderNormal` -> (image, dmap, alpha[, dist][, nmap]): the depth
+    blend, then the distortion forward if asked, then the colour blend of `normal` if given, all on one binning.  `absgrad`: the
+    Function's trailing arguments.  Saved: the inputs (`normal` as it came, None included), the transmittance checkpoints and,
+    with the distortion, its two per-pixel sums — nothing a Function does not use."""
+    _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background, normal)
+    ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
+    ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
+    with torch.no_grad():
+        bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
+        *maps, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
+                                                    with_checkpoints=True)
+        sums = ()
+        if distortion:
+            dist, *sums = _raster.blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
+            maps.append(dist)
+        if normal is not None:
+            maps.append(_raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, normal))
+    _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *sums)
+    return tuple(maps)
+
+
+def _render_backward(ctx, g_image, g_depth, g_alpha, g_dist=None, g_nmap=None):
+    """The backward of the three render Functions -> the gradients of `_render_forward`'s eleven tensor and size arguments
+    (startpoint ... background, normal).  The depth backward, then absgrad, then — only where the loss used that map — the
+    distortion backward and the normal backward (a second `blend_backward` on the image's checkpoints), each added in place in
+    this order."""
+    (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *sums), bins = _saved_with_bins(ctx)
+    want_bg = background is not None and ctx.needs_input_grad[9]
+    g_normal = None
+    with torch.no_grad():
+        g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
+            bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
+            background, background_grad=want_bg)
+        if ctx.absgrad is not None:
+            _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
+                                        g_depth, g_alpha, background, out=ctx.absgrad)
+        if g_dist is not None:
+            d_mean, d_vinv, d_op, d_z = _raster.blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                       depth, t_ckpt, *sums, g_dist)
+            g_mean += d_mean
+            g_vinv += d_vinv
+            g_op += d_op
+            g_z += d_z
+        if g_nmap is not None:
+            n_mean, n_vinv, n_op, g_normal = _raster.blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
+                                                                    normal, t_ckpt, g_nmap)
+            g_mean += n_mean
+            g_vinv += n_vinv
+            g_op += n_op
+    g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
+    return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
+            g_bg.reshape(background.shape) if want_bg else None, g_normal)
+
+
 class RenderDepth(torch.autograd.Function):
     """The Function's blend with an expected-depth map, an alpha map and a background colour (csrc/gcp_blend.hip,
     k_blend_fwd_depth / k_blend_bwd_depth); see `render`.  Capture-safe and overflow-reporting under `tile_capacity` /
     `GraphedStep` as `custom_autograd_grouped_cumprod`, and with the same optional trailing `absgrad` buffer, filled by
-    `raster.blend_absgrad_depth` for the gradients of all three maps."""
+    `raster.blend_absgrad_depth` for the gradients of all three maps.  Forward and backward are `_render_forward` /
+    `_render_backward`, which `RenderDistortion` and `RenderNormal` share."""
 
     @staticmethod
     def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
                 *absgrad):
-        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
-        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
-        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
-        with torch.no_grad():
-            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
-            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                     l_d, depth, background, with_checkpoints=True)
-        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt)
-        return image, dmap, alpha
+        return _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height,
+                               background, None, False, absgrad)
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha):
-        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt), bins = _saved_with_bins(ctx)
-        want_bg = background is not None and ctx.needs_input_grad[9]
-        with torch.no_grad():
-            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
-                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
-                background, background_grad=want_bg)
-            if ctx.absgrad is not None:
-                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
-                                            g_depth, g_alpha, background, out=ctx.absgrad)
-        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
-        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
-                g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
+        return _render_backward(ctx, g_image, g_depth, g_alpha)[:10] + (None,) * ctx.n_absgrad
 
 
 class RenderDistortion(torch.autograd.Function):
@@ -730,38 +769,12 @@ class RenderDistortion(torch.autograd.Function):
     @staticmethod
     def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
                 *absgrad):
-        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background)
-        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
-        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
-        with torch.no_grad():
-            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
-            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                     l_d, depth, background, with_checkpoints=True)
-            dist, a_n, b_n = _raster.blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
-        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, a_n, b_n)
-        return image, dmap, alpha, dist
+        return _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height,
+                               background, None, True, absgrad)
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha, g_dist):
-        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, t_ckpt, a_n, b_n), bins = _saved_with_bins(ctx)
-        want_bg = background is not None and ctx.needs_input_grad[9]
-        with torch.no_grad():
-            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
-                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
-                background, background_grad=want_bg)
-            if ctx.absgrad is not None:
-                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
-                                            g_depth, g_alpha, background, out=ctx.absgrad)
-            if g_dist is not None:
-                d_mean, d_vinv, d_op, d_z = _raster.blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                           depth, t_ckpt, a_n, b_n, g_dist)
-                g_mean += d_mean
-                g_vinv += d_vinv
-                g_op += d_op
-                g_z += d_z
-        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
-        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
-                g_bg.reshape(background.shape) if want_bg else None) + (None,) * ctx.n_absgrad
+        return _render_backward(ctx, g_image, g_depth, g_alpha, g_dist)[:10] + (None,) * ctx.n_absgrad
 
 
 class RenderNormal(torch.autograd.Function):
@@ -777,52 +790,13 @@ class RenderNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
                 normal, distortion, *absgrad):
-        _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background, normal)
-        ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
-        ctx.distortion = bool(distortion)
-        ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
-        with torch.no_grad():
-            bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
-            image, dmap, alpha, t_ckpt = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                     l_d, depth, background, with_checkpoints=True)
-            extra, saved = (), ()
-            if ctx.distortion:
-                dist, a_n, b_n = _raster.blend_distort_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
-                extra, saved = (dist,), (a_n, b_n)
-            nmap = _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, normal)
-        _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *saved)
-        return (image, dmap, alpha, *extra, nmap)
+        return _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height,
+                               background, normal, bool(distortion), absgrad)
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_alpha, *g_rest):
-        (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *saved), bins = _saved_with_bins(ctx)
-        g_dist, g_nmap = (g_rest[0] if ctx.distortion else None), g_rest[-1]
-        want_bg = background is not None and ctx.needs_input_grad[9]
-        g_normal = None
-        with torch.no_grad():
-            g_mean, g_vinv, g_op, g_l, g_z, g_bg = _raster.blend_backward_depth(
-                bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image, g_depth, g_alpha,
-                background, background_grad=want_bg)
-            if ctx.absgrad is not None:
-                _raster.blend_absgrad_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, t_ckpt, g_image,
-                                            g_depth, g_alpha, background, out=ctx.absgrad)
-            if g_dist is not None:
-                a_n, b_n = saved
-                d_mean, d_vinv, d_op, d_z = _raster.blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                           depth, t_ckpt, a_n, b_n, g_dist)
-                g_mean += d_mean
-                g_vinv += d_vinv
-                g_op += d_op
-                g_z += d_z
-            if g_nmap is not None:
-                n_mean, n_vinv, n_op, g_normal = _raster.blend_backward(bins, startpoint, endpoint, mean, variance_inverse, opacity,
-                                                                        normal, t_ckpt, g_nmap)
-                g_mean += n_mean
-                g_vinv += n_vinv
-                g_op += n_op
-        g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
-        return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
-                g_bg.reshape(background.shape) if want_bg else None, g_normal, None) + (None,) * ctx.n_absgrad
+        g_dist, g_nmap = g_rest if len(g_rest) == 2 else (None, *g_rest)  # (g_dist, g_nmap) with the distortion, else (g_nmap,)
+        return _render_backward(ctx, g_image, g_depth, g_alpha, g_dist, g_nmap) + (None,) * (1 + ctx.n_absgrad)
 
 
 def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None,
@@ -858,17 +832,15 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
     the weights, in mean (if float), variance_inverse and opacity.  The other maps are the same bits with and without it, it
     combines with `distortion=True` ((image, depth, alpha, dist, nmap)), a loss that does not use nmap launches nothing extra in
     backward and gets the other call's gradients bit for bit, and `absgrad` is filled from the three maps' gradients only."""
+    fn, extra = (RenderDistortion if distortion else RenderDepth), ()
     if normal is not None:
         n = startpoint.shape[0]
         if not (isinstance(normal, torch.Tensor) and tuple(normal.shape) == (n, 3) and normal.device == startpoint.device):
             raise RuntimeError(f"normal: expected an [{n}, 3] tensor on {startpoint.device} (normals.gaussian_normals), or None")
-        extra = () if absgrad is None else (absgrad,)
-        return RenderNormal.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
-                                  normal, bool(distortion), *extra)
-    fn = RenderDistortion if distortion else RenderDepth
-    if absgrad is None:
-        return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background)
-    return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, absgrad)
+        fn, extra = RenderNormal, (normal, bool(distortion))
+    if absgrad is not None:
+        extra += (absgrad,)
+    return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, *extra)
 
 
 def contribution(startpoint, endpoint, mean, variance_inverse, opacity, image_width, image_height):
@@ -887,14 +859,13 @@ def paint(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_widt
     device or None) paints from the same arguments -> (H+1, W+1, 3), detached, for evaluation: bins, then `raster.blend_forward`
     / `raster.blend_forward_depth` WITHOUT transmittance checkpoints — nothing is kept for a backward, there is no autograd
     node.  Under `tile_capacity` the bins are the capture-safe ones, as in the Functions.  GPU tensors only."""
+    if depth is not None:
+        return paint_maps(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth, background)[0]
     with torch.no_grad():
         bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
-        if depth is None:
-            if background is not None:
-                raise RuntimeError("paint: a background is composited by the depth blend: pass the Gaussians' depths")
-            return _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False)
-        return _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
-                                           with_checkpoints=False)[0]
+        if background is not None:
+            raise RuntimeError("paint: a background is composited by the depth blend: pass the Gaussians' depths")
+        return _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False)
 
 
 def paint_maps(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth, background=None):

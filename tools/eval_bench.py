@@ -27,7 +27,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from densify_bench import HBM_PEAK, median, timed  # noqa: E402
+from densify_bench import HBM_PEAK, median  # noqa: E402
+from exposure_bench import passes_of  # noqa: E402
 from simplegaussiansplat_tk71_amd import _lib, loss, synthetic  # noqa: E402
 from simplegaussiansplat_tk71_amd import gs_model as gm  # noqa: E402
 
@@ -74,29 +75,15 @@ def measure(shape, windows, window_s, dev):
                                            stream), "gcp_ssim_l1_forward")
 
     variants = {"image_metrics": metrics, "loss_forward_no_maps": loss_forward, "torch_float32": lambda: torch_metrics(a, b, window)}
-    calls = {}
-    for k, call in variants.items():  # warm-up, then the number of calls that fills a window
-        for _ in range(5):
-            call()
-        ms = timed(lambda: [call() for _ in range(10)])[0] / 10
-        calls[k] = max(10, int(1.25 * window_s * 1e3 / ms) + 1)
-    passes = []
-    for _ in range(2):
-        t = {k: [] for k in variants}
-        for _ in range(windows):
-            for k, call in variants.items():
-                total = timed(lambda: [call() for _ in range(calls[k])])[0]
-                assert total >= window_s * 1e3 or k == "torch_float32", (k, total)
-                t[k].append(total / calls[k])
-        passes.append({k: median(v) for k, v in t.items()})
+    # the windows of exposure_bench: its calibration measures whole windows (ten calls alone overestimate a call by a quarter,
+    # and a window sized by them fell short of `window_s`)
     moved = 8 * bsz * ch * h * w
     res = {}
-    for k in variants:
-        p1, p2 = passes[0][k], passes[1][k]
+    for k, (p1, p2, n_calls) in passes_of(variants, windows, window_s).items():
         res[k] = {"measurement": "per-image metrics", "variant": k, "shape": list(shape), "ms_pass_1": round(p1, 5), "ms_pass_2": round(p2, 5),
                   "ms_median": round(0.5 * (p1 + p2), 5), "spread": round(abs(p1 - p2) / min(p1, p2), 4), "bytes_needed": moved,
                   "tb_per_s": round(moved / (0.5 * (p1 + p2)) / 1e9, 3), "share_of_hbm_peak": round(moved / (0.5 * (p1 + p2) * 1e-3) / HBM_PEAK, 3),
-                  "calls_per_window": calls[k], "windows_per_pass": windows}
+                  "calls_per_window": n_calls, "windows_per_pass": windows}
     got = [t.cpu() for t in torch_metrics(a, b, window)]  # the two formulations agree on what they measured
     res["image_metrics"]["max_abs_difference_to_torch_float32"] = max(float((out[:, i].cpu() - got[i].double()).abs().max()) for i in range(3))
     new, old = res["image_metrics"], res["loss_forward_no_maps"]
