@@ -355,10 +355,12 @@ int gcp_pairs_scan_boxes(const int32_t* start_xy, const int32_t* end_xy, int64_t
 
 /* The walk writing the FINAL values of _create_alpha_brend (gs_model.py:557-564), so that a list that drops nothing needs no
  * compaction pass at all.  Same walk as gcp_pairs_scan_boxes, same arguments, but every pair receives
- *   values[pair] = inclusive / x[pair] (mode 0, gs_model.py:562)  or  inclusive - x[pair] (modes 1, 2, :564)
- * — the fp32 operation gcp_compact_finish would apply to the stored inclusive value: the same bits — and
  *   keep[pair]   = (inclusive != 0)                                  (gs_model.py:560, :575-578)
- * as one byte per pair (the call sets every byte to 1 and the walk clears the bytes of the pairs it drops);
+ * as one byte per pair (the call sets every byte to 1 and the walk clears the bytes of the pairs it drops), and every KEPT pair
+ *   values[pair] = inclusive / x[pair] (mode 0, gs_model.py:562)  or  inclusive - x[pair] (modes 1, 2, :564)
+ * — the fp32 operation gcp_compact_finish would apply to the stored inclusive value: the same bits.  values[pair] of a dropped
+ * pair is unspecified: in mode 0 a wave whose 64 pixels have all reached the product 0 stores nothing there (whatever the
+ * buffer held stays), and gcp_compact_kept_write moves kept values only;
  * dropped_per_tile (required, int32[ceil(n_pairs / 4096)]) counts them per 4096 consecutive pairs.  prepared != 0: the
  * caller has already run gcp_pairs_finish_prepare(keep, dropped_per_tile, n_pairs, stream) on the same stream — the two
  * fills, which depend on nothing but n_pairs, can then be queued BEFORE the host waits for gcp_rects_cut's info8 and run

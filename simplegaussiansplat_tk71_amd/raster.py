@@ -591,6 +591,8 @@ def finish_boxes(bins, startpoint, endpoint, box_off, values, mode, buffers=None
     """The walk of `scan_boxes` writing the FINAL values of _create_alpha_brend (gs_model.py:557-564) instead of the inclusive
     ones: -> (final f32[M] = inclusive / self (mode 0) or inclusive - self (modes 1, 2), keep uint8[M] = inclusive != 0,
     dropped int32[ceil(M / 4096)]).  Hand all three to `compact_kept`: when nothing was dropped they ARE the result.
+    Where `keep` is 0 the pair is dropped and its `final` is unspecified: a wave whose 64 pixels have all reached the product 0
+    clears the bytes of the rest of its list and stores no values there (`compact_kept` moves kept values only).
     buffers: what `finish_buffers(values)` returned on this stream (already initialised)."""
     start = _dev_tensor(startpoint, "startpoint", torch.int32, (2,))
     end = _dev_tensor(endpoint, "endpoint", torch.int32, (2,))
