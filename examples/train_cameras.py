@@ -129,7 +129,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
           screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
           exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000, save_mesh=None, mesh_resolution=256,
-          mesh_trunc=None):
+          mesh_trunc=None, normal_depth="expected", mesh_depth="expected"):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -196,6 +196,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `ply_io.save_mesh`; `batch_size` cameras at a time; a running mean is order-dependent, so the ranks do not share the work).
     `mesh_resolution` = 256 and the default truncation of 5 voxels are pointers from 2DGS's usage, not tuned here.  With
     save_mesh=None (the default) no step and no output changes.
+    `normal_depth` / `mesh_depth` "median": the depth surface of the normal term / the fused depth is the median depth map
+    (`model.render(median=True)` through `gs_model.median_as_depth`; `model.extract_mesh(depth="median")`) instead of the
+    expected depth — 2DGS's depth_ratio = 1 for bounded scenes, a pointer and not a tuned choice.  With "expected" (the
+    default) no step and no output changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -284,6 +288,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
             if mine.numel():
                 distort = distortion_reg > 0 and iteration >= distortion_from
                 with_normals = normal_reg > 0 and iteration >= normal_from
+                with_median = with_normals and normal_depth == "median"
                 dist = nmaps = None
                 if background is None and not distort and not with_normals:
                     images, kept, grad_iter = model(P[mine], K[mine], wh[mine], mine.tolist())
@@ -294,10 +299,13 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
                         bg = torch.rand(3, device=dev) if isinstance(background, str) else torch.as_tensor(background, dtype=torch.float32,
                                                                                                               device=dev)
                     images, *maps, kept, grad_iter = model.render(P[mine], K[mine], wh[mine], background=bg, image_sample=mine.tolist(),
-                                                                  distortion=distort, **({"normals": True} if with_normals else {}))
+                                                                  distortion=distort, **({"normals": True} if with_normals else {}),
+                                                                  **({"median": True} if with_median else {}))
                     dist = maps[2] if distort else None
                     sel = torch.tensor(kept, device=dev)
-                    if with_normals:
+                    if with_median:  # the depth surface from the median map; the blended normals as before
+                        nmaps = (*gm.median_as_depth(maps[-1], maps[1]), maps[-2], K[sel])
+                    elif with_normals:
                         nmaps = (maps[0], maps[1], maps[-1], K[sel])
                     target = targets[sel]
                     if bg is not None and target_alpha is not None:
@@ -390,7 +398,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     if save_mesh is not None and rank == 0:
         from simplegaussiansplat_tk71_amd import ply_io
 
-        vertices, faces, colours = model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc, batch_size=batch_size)
+        vertices, faces, colours = model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc, batch_size=batch_size,
+                                                      **({"depth": "median"} if mesh_depth == "median" else {}))
         ply_io.save_mesh(save_mesh, vertices, faces, colours)
         log(f"mesh: {vertices.shape[0]} vertices, {faces.shape[0]} faces -> {save_mesh}")
     return model, losses
@@ -470,6 +479,13 @@ def build_parser():
     ap.add_argument("--exposure-lr-init", type=float, default=0.01, help="with --exposure: the first learning rate (upstream's, not tuned here)")
     ap.add_argument("--exposure-lr-final", type=float, default=0.001, help="with --exposure: the rate after 30 000 steps (upstream's)")
     ap.add_argument("--save-exposure", default=None, metavar="PATH", help="with --exposure: write the matrices as JSON, image name -> 3 x 4 list")
+    ap.add_argument("--normal-depth", choices=("expected", "median"), default="expected",
+                    help="with --normal-reg: the depth whose surface normals the blended normals are held against: the expected depth "
+                         "sum w z / alpha, or the median depth, the layer at which the transmittance falls through 1/2 (2DGS's "
+                         "depth_ratio = 1 for bounded scenes: a pointer, not a tuned choice)")
+    ap.add_argument("--mesh-depth", choices=("expected", "median"), default="expected",
+                    help="with --save-mesh: the depth map that is fused, as for --normal-depth (2DGS's depth_ratio = 1 fuses the "
+                         "median depth of bounded scenes: a pointer, not a tuned choice)")
     ap.add_argument("--save-mesh", default=None, metavar="PATH",
                     help="after the last step: fuse the training cameras' depth maps into a TSDF volume and write its surface as a "
                          "triangle mesh .ply (rank 0); what --normal-reg and --distortion-reg shape the depth for")
@@ -520,7 +536,8 @@ if __name__ == "__main__":
                       screen_grad=a.screen_grad, distortion_reg=a.distortion_reg, distortion_from=a.distortion_from,
                       filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
                       exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure, normal_reg=a.normal_reg,
-                      normal_from=a.normal_from, save_mesh=a.save_mesh, mesh_resolution=a.mesh_resolution, mesh_trunc=a.mesh_trunc)
+                      normal_from=a.normal_from, save_mesh=a.save_mesh, mesh_resolution=a.mesh_resolution, mesh_trunc=a.mesh_trunc,
+                      normal_depth=a.normal_depth, mesh_depth=a.mesh_depth)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -925,6 +925,39 @@ int gcp_blend_distort_backward(const int32_t* start_xy, const int32_t* end_xy, c
                                const float* grad_dist, float* grad_mean, float* grad_vinv, float* grad_opacity,
                                float* grad_depth, void* ws, size_t ws_bytes, void* stream);
 
+/* Median depth of one camera (gcp_median.hip; 2DGS's depth_ratio = 1, gsplat's 2DGS mode, RaDe-GS): the depth of the layer at
+ * which the pixel's transmittance falls through 1/2.  The pair rule is gcp_blend_forward's to the letter, for pixel p of the
+ * (H+1) x (W+1) frame over its list front to back: a pair must lie inside the integer box clamped to the frame,
+ * g = exp(-1/2 d Λ d^T), T_k is the exclusive product of 1 - o g, w_k = T_k o_k g_k, and a pair whose inclusive product is
+ * exactly 0 is dropped (w = 0).  A pair CONTRIBUTES iff w_k != 0 (the distortion's notion of a contributing pair).
+ *   m(p)            = the LAST contributing pair k of p with T_k > 0.5   (strict)
+ *   median(p)       = z_m          — a copy of depth[m], not an interpolation, NOT multiplied by alpha
+ *   median_index(p) = the Gaussian's row in the call's arrays (what tile_list holds), int32
+ *   median(p) = 0, median_index(p) = -1 where p has no contributing pair
+ * — 2DGS's `if (T > 0.5) { median_depth = depth; median_contributor = ...; }`.  Where the pixel's transmittance crosses 1/2, m
+ * is the layer that crosses it; where it never does (alpha < 1/2), the pixel's last contributing layer; behind an exactly
+ * opaque dropped pair, the last contributing pair in front of it.  The forward uses the arithmetic of the forward blend,
+ * contraction included: the T compared with 1/2 is the T the image was painted with.  It stops walking a tile's list once no
+ * pixel of the tile is above 1/2, which changes no bit of either output.  It writes median_map (float) and median_index
+ * (int32), (H+1)(W+1) each, and uses no checkpoints.  n_gauss == 0: median_map is 0 and median_index -1 everywhere.
+ * Backward: median is piecewise constant in everything but z_m,
+ *   dL/dz_g = sum_{p : median_index(p) = g} G(p),  G = grad_median = dL/d median;   zero to mean, vinv and opacity
+ * summed per tile in pixel order into the Gaussian-major slot of the (tile, Gaussian) entry, then per Gaussian over its slots
+ * in order: no float atomics, two calls give the same bits.  median_index: what the forward wrote ON THE SAME BINS (an index
+ * that is not a row whose box reaches the pixel's tile is ignored).  It WRITES grad_depth [N]: 0 for a Gaussian no pixel
+ * picked and for one the binning did not list.  n_gauss == 0: nothing is touched; n_tile_pairs == 0: grad_depth is zeroed.
+ * No stream synchronise, no read-back, no allocation.
+ * ws: gcp_blend_median_backward_workspace_bytes(K) (4 bytes per entry). */
+int gcp_blend_median_forward(const int32_t* start_xy, const int32_t* end_xy, const float* mean_xy, const float* vinv,
+                             const float* opacity, const float* depth, int64_t n_gauss, int32_t width, int32_t height,
+                             const int32_t* tile_start, const int32_t* tile_list, float* median_map, int32_t* median_index,
+                             void* stream);
+size_t gcp_blend_median_backward_workspace_bytes(int64_t n_tile_pairs);
+int gcp_blend_median_backward(const int32_t* start_xy, const int32_t* end_xy, int64_t n_gauss, int32_t width, int32_t height,
+                              const int32_t* tile_off, int64_t n_tile_pairs, const int32_t* tile_start,
+                              const int32_t* median_index, const float* grad_median, float* grad_depth, void* ws, size_t ws_bytes,
+                              void* stream);
+
 /* ---- the 3-D smoothing filter of Mip-Splatting (Yu et al., CVPR 2024; csrc/gcp_filter3d.hip) ---------------------------
  * A stage in FRONT of the projection: every Gaussian is low-pass filtered in world space by an isotropic Gaussian of size
  * filter[i] = phi >= 0 (the caller forms it from the sampling rate: phi = sqrt(0.2) / rate in the published code) and its

@@ -162,6 +162,10 @@ SIGNATURES = {
     "gcp_blend_distort_forward": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32] + [_c_void_p] * 6),
     "gcp_blend_distort_backward_workspace_bytes": (_sz, [_i64]),
     "gcp_blend_distort_backward": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 11 + [_sz, _c_void_p]),
+    # median depth (gcp_median.hip): forward -> median f32 and index i32 maps; backward: boxes, bins, index and grad_median -> grad_depth
+    "gcp_blend_median_forward": (ctypes.c_int, [_c_void_p] * 6 + [_i64, _i32, _i32] + [_c_void_p] * 5),
+    "gcp_blend_median_backward_workspace_bytes": (_sz, [_i64]),
+    "gcp_blend_median_backward": (ctypes.c_int, [_c_void_p] * 2 + [_i64, _i32, _i32, _c_void_p, _i64] + [_c_void_p] * 5 + [_sz, _c_void_p]),
     # the 3-D smoothing filter (gcp_filter3d.hip): rate (mean, P, K, wh, n, cameras, near, margin -> rate); apply (log scale, opacity,
     # filter, n -> the filtered two); its backward (the three inputs, the two upstream gradients, n -> the two gradients); stream last
     "gcp_filter3d_rate": (ctypes.c_int, [_c_void_p] * 4 + [_i64, _i64, ctypes.c_float, ctypes.c_float, _c_void_p, _c_void_p]),

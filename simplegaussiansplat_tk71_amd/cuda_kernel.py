@@ -66,6 +66,7 @@ __all__ = [
     "RenderDepth",
     "RenderDistortion",
     "RenderNormal",
+    "RenderMedian",
     "render",
     "contribution",
     "absgrad_buffer",
@@ -684,11 +685,12 @@ class custom_autograd_grouped_cumprod(torch.autograd.Function):
 
 
 def _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, normal,
-                    distortion, absgrad):
-    """The forward of `RenderDepth`, `RenderDistortion` and `RenderNormal` -> (image, dmap, alpha[, dist][, nmap]): the depth
-    blend, then the distortion forward if asked, then the colour blend of `normal` if given, all on one binning.  `absgrad`: the
-    Function's trailing arguments.  Saved: the inputs (`normal` as it came, None included), the transmittance checkpoints and,
-    with the distortion, its two per-pixel sums — nothing a Function does not use."""
+                    distortion, absgrad, median=False):
+    """The forward of `RenderDepth`, `RenderDistortion`, `RenderNormal` and `RenderMedian` -> (image, dmap, alpha[, dist][, nmap]
+    [, median]): the depth blend, then the distortion forward if asked, then the colour blend of `normal` if given, then the
+    median walk if asked, all on one binning.  `absgrad`: the Function's trailing arguments.  Saved: the inputs (`normal` as it
+    came, None included), the transmittance checkpoints, with the distortion its two per-pixel sums and, with the median, its
+    index map, last — nothing a Function does not use."""
     _refuse_stale_leaves_in_capture(mean, variance_inverse, opacity, l_d, depth, background, normal)
     ctx.absgrad = _absgrad_argument(ctx, absgrad, startpoint)
     ctx.set_materialize_grads(False)  # an output nobody uses hands its kernel a NULL gradient, not a buffer of zeros
@@ -702,16 +704,23 @@ def _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, 
             maps.append(dist)
         if normal is not None:
             maps.append(_raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, normal))
+        ctx.median = bool(median)
+        if median:
+            med, index = _raster.blend_median_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)
+            maps.append(med)
+            sums = (*sums, index)
     _save_with_bins(ctx, bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *sums)
     return tuple(maps)
 
 
-def _render_backward(ctx, g_image, g_depth, g_alpha, g_dist=None, g_nmap=None):
-    """The backward of the three render Functions -> the gradients of `_render_forward`'s eleven tensor and size arguments
+def _render_backward(ctx, g_image, g_depth, g_alpha, g_dist=None, g_nmap=None, g_median=None):
+    """The backward of the render Functions -> the gradients of `_render_forward`'s eleven tensor and size arguments
     (startpoint ... background, normal).  The depth backward, then absgrad, then — only where the loss used that map — the
-    distortion backward and the normal backward (a second `blend_backward` on the image's checkpoints), each added in place in
-    this order."""
+    distortion backward, the normal backward (a second `blend_backward` on the image's checkpoints) and the median backward
+    (grad_depth alone), each added in place in this order."""
     (startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background, normal, t_ckpt, *sums), bins = _saved_with_bins(ctx)
+    if ctx.median:
+        *sums, m_index = sums
     want_bg = background is not None and ctx.needs_input_grad[9]
     g_normal = None
     with torch.no_grad():
@@ -734,6 +743,8 @@ def _render_backward(ctx, g_image, g_depth, g_alpha, g_dist=None, g_nmap=None):
             g_mean += n_mean
             g_vinv += n_vinv
             g_op += n_op
+        if g_median is not None:
+            g_z += _raster.blend_median_backward(bins, startpoint, endpoint, m_index, g_median)
     g_mean = g_mean if mean.is_floating_point() else None  # integer means carry no gradient
     return (None, None, g_mean, g_vinv, g_op.reshape(opacity.shape), g_l, g_z.reshape(depth.shape), None, None,
             g_bg.reshape(background.shape) if want_bg else None, g_normal)
@@ -799,8 +810,32 @@ class RenderNormal(torch.autograd.Function):
         return _render_backward(ctx, g_image, g_depth, g_alpha, g_dist, g_nmap) + (None,) * (1 + ctx.n_absgrad)
 
 
+class RenderMedian(torch.autograd.Function):
+    """Any of the three Functions above with one more output, always last: the per-pixel median depth map (csrc/gcp_median.hip,
+    k_median_fwd on the bins of the blend; see `render(median=True)`), differentiable in `depth` only — its index map is kept
+    for the backward (k_median_bwd / k_median_reduce) and is not an output.  The other maps come from the same kernels as
+    without it: the same bits; when the loss does not use the median its gradient arrives as None, no median kernel is launched
+    and the gradients are the sibling's bit for bit.  Capture-safe and overflow-reporting like the other Functions; the optional
+    trailing `absgrad` buffer is filled from the gradients of the THREE maps only."""
+
+    @staticmethod
+    def forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background,
+                normal, distortion, *absgrad):
+        ctx.n_rest = int(bool(distortion)) + int(normal is not None)
+        ctx.distortion = bool(distortion)
+        return _render_forward(ctx, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height,
+                               background, normal, bool(distortion), absgrad, median=True)
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_alpha, *g_rest):
+        *g_rest, g_median = g_rest  # ([g_dist,] [g_nmap,] g_median)
+        g_dist = g_rest[0] if ctx.distortion else None
+        g_nmap = g_rest[-1] if ctx.n_rest > int(ctx.distortion) else None
+        return _render_backward(ctx, g_image, g_depth, g_alpha, g_dist, g_nmap, g_median) + (None,) * (1 + ctx.n_absgrad)
+
+
 def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background=None, absgrad=None,
-           distortion=False, normal=None):
+           distortion=False, normal=None, median=False):
     """Rasterise and blend one camera's depth-ordered Gaussians (the arguments of `custom_autograd_grouped_cumprod`, without
     boxsize / batch) -> (image (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), differentiable in mean (if float),
     variance_inverse, opacity, l_d, depth and background.
@@ -831,13 +866,23 @@ def render(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, im
     NOT divided by alpha, no background — painted by the colour blend on the same bins, differentiable in `normal` and, through
     the weights, in mean (if float), variance_inverse and opacity.  The other maps are the same bits with and without it, it
     combines with `distortion=True` ((image, depth, alpha, dist, nmap)), a loss that does not use nmap launches nothing extra in
-    backward and gets the other call's gradients bit for bit, and `absgrad` is filled from the three maps' gradients only."""
+    backward and gets the other call's gradients bit for bit, and `absgrad` is filled from the three maps' gradients only.
+    `median=True` (`RenderMedian`) -> one more map, always last ((image, depth, alpha[, dist][, nmap], median)): the median depth
+    (H+1, W+1) — with m the LAST contributing pair (w_k != 0) of the pixel whose exclusive transmittance T_k > 0.5 (strict),
+    median(p) = depth[m]: a copy, not an interpolation and NOT multiplied by alpha; 0 where the pixel has no contributing pair
+    (2DGS's depth_ratio = 1; `raster.blend_median_forward`).  Where the transmittance crosses 1/2 it is the depth of the layer
+    that crosses it, elsewhere of the pixel's last layer.  Differentiable in `depth` only (dL/dz_g = the sum of the upstream
+    gradient over the pixels that picked g): piecewise constant in everything else.  The other maps are the same bits with and
+    without it, a loss that does not use it launches no median kernel in backward and gets the other call's gradients bit for
+    bit, and `absgrad` is filled from the three maps' gradients only."""
     fn, extra = (RenderDistortion if distortion else RenderDepth), ()
     if normal is not None:
         n = startpoint.shape[0]
         if not (isinstance(normal, torch.Tensor) and tuple(normal.shape) == (n, 3) and normal.device == startpoint.device):
             raise RuntimeError(f"normal: expected an [{n}, 3] tensor on {startpoint.device} (normals.gaussian_normals), or None")
         fn, extra = RenderNormal, (normal, bool(distortion))
+    if median:
+        fn, extra = RenderMedian, (normal, bool(distortion))
     if absgrad is not None:
         extra += (absgrad,)
     return fn.apply(startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, image_width, image_height, background, *extra)
@@ -868,12 +913,17 @@ def paint(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_widt
         return _raster.blend_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, with_checkpoints=False)
 
 
-def paint_maps(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth, background=None):
+def paint_maps(startpoint, endpoint, mean, variance_inverse, opacity, l_d, image_width, image_height, depth, background=None, median=False):
     """What `paint` does with `depth` [N] given, but all three maps `render` paints from the same arguments -> (image
     (H+1, W+1, 3), depth (H+1, W+1), alpha (H+1, W+1)), detached: bins, then `raster.blend_forward_depth` WITHOUT transmittance
     checkpoints, no autograd node.  The image is `paint(..., depth=depth, background=background)` bit for bit; the depth map is
-    NOT divided by alpha.  What `mesh.TSDFVolume.integrate` fuses (after the [1:, 1:] crop).  GPU tensors only."""
+    NOT divided by alpha.  What `mesh.TSDFVolume.integrate` fuses (after the [1:, 1:] crop).  `median=True`: one more map, last,
+    the median depth of `render(median=True)` on the same bins (`raster.blend_median_forward`; its index map is dropped).
+    GPU tensors only."""
     with torch.no_grad():
         bins = _bin_sticky(startpoint, endpoint, image_width, image_height)
-        return _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
+        maps = _raster.blend_forward_depth(bins, startpoint, endpoint, mean, variance_inverse, opacity, l_d, depth, background,
                                            with_checkpoints=False)
+        if median:
+            maps = (*maps, _raster.blend_median_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth)[0])
+        return maps

@@ -10,7 +10,7 @@ it and is re-exported from here under the names it always had: the camera projec
 the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`) and the kernels of the density control
 (density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
 `apply_filter`), the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`) and the
-normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`) and the mesh extraction
+normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`, `median_as_depth`) and the mesh extraction
 (mesh.py: `TSDFVolume`, `extract_surface`).
 Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
@@ -35,7 +35,7 @@ from .filter3d import apply_filter, filter_from_rate, sampling_rate
 from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
 from .mesh import TSDFVolume, extract_surface
-from .normals import depth_normals, gaussian_normals, normal_consistency, normal_consistency_map
+from .normals import depth_normals, gaussian_normals, median_as_depth, normal_consistency, normal_consistency_map
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
 
@@ -66,6 +66,7 @@ __all__ = [
     "qvec_to_rotmat_batch",
     "get_expon_lr_func",
     "mean_neighbour_distance",
+    "median_as_depth",
     "normal_consistency",
     "normal_consistency_map",
     "sampling_rate",
@@ -715,7 +716,7 @@ class GS_model_with_param(torch.nn.Module):
         out = out.reshape(-1, 3, h, w) if self.reference_layout else out.permute(0, 3, 1, 2).contiguous()
         return [out, names, grad_iter]
 
-    def render(self, P, K, wh, background=None, image_sample=None, distortion=False, normals=False):
+    def render(self, P, K, wh, background=None, image_sample=None, distortion=False, normals=False, median=False):
         """`forward` with the expected-depth and alpha maps and a background colour (`cuda_kernel.render`, whose
         docstring pins the definitions: depth = sum of the colour weights times the camera-space depth, NOT divided by
         alpha; alpha = 1 - the transmittance behind the pixel; image composited over `background`, a float[3] device tensor
@@ -731,7 +732,12 @@ class GS_model_with_param(torch.nn.Module):
         normals of its list come from `gaussian_normals` on the RAW parameters (variance_q, variance_scale, mean; the 3-D
         filter does not change which axis is the shortest) and `cam["index"]`, and are blended by
         `cuda_kernel.render(normal=)`; their gradient reaches variance_q, the map's weights' the other parameters.  What
-        `normal_consistency(depth, alpha, normal, K)` takes.  The other maps are the same bits as without it."""
+        `normal_consistency(depth, alpha, normal, K)` takes.  The other maps are the same bits as without it.
+        median=True: one more map after every other map and before `names`, median (B, 1, H, W): the median depth of
+        `cuda_kernel.render(median=True)` (the depth of the layer at which the pixel's transmittance falls through 1/2; a copy
+        of one Gaussian's depth, NOT multiplied by alpha; 2DGS's depth_ratio = 1), cropped like the others; its gradient reaches
+        the parameters through that Gaussian's camera-space depth alone.  `median_as_depth(median, alpha)` turns it into the
+        pair `normal_consistency` and `TSDFVolume.integrate` take.  The other maps are the same bits as without it."""
         cams, grad_iter, (width, height) = self.camera_inputs(P, K, wh, with_depth=True)
         self._watch_centres(cams, width, height)
         if normals:
@@ -742,13 +748,14 @@ class GS_model_with_param(torch.nn.Module):
             cams, range(P.shape[0]) if image_sample is None else image_sample,
             lambda cam: render(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"], cam["l_d"],
                                cam["depth"], width, height, background, cam.get("absgrad"), distortion=distortion,
-                               normal=cam.get("normal")))
+                               normal=cam.get("normal"), median=median))
         images = maps[0][:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous()
+        tail = [maps.pop()[:, None, 1:, 1:].contiguous()] if median else []  # the median is always the last map
         n_planes = len(maps) - (2 if normals else 1)
         planes = [m[:, None, 1:, 1:].contiguous() for m in maps[1:1 + n_planes]]  # depth, alpha[, distortion]
         if normals:
             planes.append(maps[-1][:, 1:, 1:, :].permute(0, 3, 1, 2).contiguous())
-        return [images, *planes, names, grad_iter]
+        return [images, *planes, *tail, names, grad_iter]
 
     @torch.no_grad()
     def evaluate(self, P, K, wh, targets, background=None, batch_size=4, clamp=True, exposure=None):
@@ -796,7 +803,8 @@ class GS_model_with_param(torch.nn.Module):
 
     # ---- mesh extraction (mesh.py, csrc/gcp_tsdf.hip) ---------------------------------------------------------------------------
     @torch.no_grad()
-    def extract_mesh(self, P, K, wh, resolution=256, bounds=None, trunc=None, alpha_min=0.5, depth_max=None, batch_size=4, colour=True):
+    def extract_mesh(self, P, K, wh, resolution=256, bounds=None, trunc=None, alpha_min=0.5, depth_max=None, batch_size=4, colour=True,
+                     depth="expected"):
         """A triangle mesh of the scene -> (vertices float32 (V, 3), faces int32 (F, 3), colours float32 (V, 3) or None): the
         depth maps of the cameras (P, K, wh) — pass the TRAINING cameras — fused into a truncated signed distance volume
         (`TSDFVolume.integrate`), its zero level set extracted by marching tetrahedra (`TSDFVolume.extract`); what 2DGS, GOF,
@@ -811,10 +819,18 @@ class GS_model_with_param(torch.nn.Module):
         beyond it are not fused, default the longest side (2 r); 0 = no limit.  `alpha_min`: pixels fainter than this are not
         fused.  resolution = 256, 5 voxels and alpha_min = 0.5 are pointers from 2DGS and Open3D usage; they are not tuned here.
         colour=False: no colour volume, colours is None.
-        Mean-depth fusion of a bounded scene only: no median depth, no mesh cleaning, no vertex normals.
+        `depth`: "expected" (the default) fuses the expected depth sum w z / alpha; "median" the median depth of
+        `cuda_kernel.paint_maps(median=True)` through `median_as_depth` — the depth of the layer at which the transmittance falls
+        through 1/2, which lies on a surface at an occlusion edge and behind a faint floater, where the mean lies between the
+        surfaces (2DGS's depth_ratio = 1 for bounded scenes: a pointer, not a tuned choice).  `alpha_min` gates on the real alpha
+        either way.
+        A bounded scene only: no mesh cleaning, no vertex normals.
         Nothing of the training state is touched: no `.grad`, no densification statistic, no optimiser state, no generator —
         like `evaluate`.  The host reads are those of the projection and the binning, and one for the mesh's size.  GPU only."""
         n_cam, dev = P.shape[0], self.mean.device
+        if depth not in ("expected", "median"):
+            raise RuntimeError(f'depth: "expected" or "median", got {depth!r}')
+        use_median = depth == "median"
         if not self.mean.is_cuda:
             raise RuntimeError("extract_mesh runs HIP kernels: the model must live on the GPU (no CPU path)")
         resolution = int(resolution)
@@ -847,11 +863,17 @@ class GS_model_with_param(torch.nn.Module):
                 if cam is None:  # nothing in view: alpha = 0 everywhere, no lattice point is updated
                     frames.append((torch.zeros(height + 1, width + 1, 3, dtype=torch.float32, device=dev),
                                    torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev),
-                                   torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev)))
+                                   torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev))
+                                  + ((torch.zeros(height + 1, width + 1, dtype=torch.float32, device=dev),) if use_median else ()))
+                elif use_median:
+                    frames.append(_paint_maps(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
+                                              cam["l_d"], width, height, cam["depth"], median=True))
                 else:
                     frames.append(_paint_maps(cam["startpoint"], cam["endpoint"], cam["mean"], cam["variance_inverse"], cam["opacity"],
                                               cam["l_d"], width, height, cam["depth"]))
-            image, depth, alpha = (torch.stack(maps, dim=0) for maps in zip(*frames))
+            image, depth, alpha, *rest = (torch.stack(maps, dim=0) for maps in zip(*frames))
+            if use_median:
+                depth, alpha = median_as_depth(rest[0], alpha)
             volume.integrate(depth[:, None, 1:, 1:], alpha[:, None, 1:, 1:], Pb.to(dev), Kb.to(dev),
                              image=image[:, 1:, 1:, :].permute(0, 3, 1, 2) if colour else None, alpha_min=alpha_min, depth_max=depth_max)
         return volume.extract()

@@ -134,6 +134,15 @@ def normal_consistency(depth, alpha, normal, K, alpha_min=ALPHA_MIN):
     return _NormalConsistency.apply(depth, alpha, normal, K, float(alpha_min))
 
 
+def median_as_depth(median, alpha):
+    """The median depth map of `render(median=True)` as the pair `normal_consistency`, `depth_normals` and
+    `TSDFVolume.integrate` take — "(depth NOT divided by alpha, alpha)" -> (median * alpha.detach(), alpha.detach()).  Those
+    kernels stay as they are and recover the median by their own division.  No gradient reaches alpha through either: the
+    median depth does not depend on alpha, and the product only undoes the consumers' division."""
+    a = alpha.detach()
+    return median * a, a
+
+
 @torch.no_grad()
 def normal_consistency_map(depth, alpha, normal, K, alpha_min=ALPHA_MIN):
     """The per-pixel term of `normal_consistency` -> (e float32 (B, 1, H, W), defined bool (B, 1, H, W)), detached: e = 1 where

@@ -1,6 +1,6 @@
 """Tile binning and fused alpha blending on the HIP library.
 
-Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_absgrad.hip, gcp_distort.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
+Host side of csrc/gcp_bin.hip, gcp_blend.hip, gcp_contrib.hip, gcp_absgrad.hip, gcp_distort.hip, gcp_median.hip, gcp_sort.hip, gcp_walk.hip and gcp_compact.hip: allocates buffers with torch, passes raw pointers through the C ABI
 (include/grouped_cumprod_hip.h).  Everything the reference does around its scan in
 `custom_autograd_grouped_cumprod` (reference: gs_model.py:598-663) happens in three launches here:
 bin (f2), blend forward (f1), blend backward (f1).  No CPU path.
@@ -444,6 +444,66 @@ def blend_distort_backward(bins, startpoint, endpoint, mean, variance_inverse, o
             "gcp_blend_distort_backward",
         )
     return tuple(grads)
+
+
+def blend_median_forward(bins, startpoint, endpoint, mean, variance_inverse, opacity, depth):
+    """The per-pixel median depth on the bins `blend_forward_depth` paints (gcp_blend_median_forward, csrc/gcp_median.hip; 2DGS's
+    depth_ratio = 1) -> (median f32[H+1, W+1], index i32[H+1, W+1]).  Per pixel, over its pairs front to back with the forward
+    blend's pair rule (w_k = T_k o_k g_k, T_k the exclusive transmittance, a pair whose inclusive product is exactly 0 dropped; a
+    pair contributes iff w_k != 0), m is the LAST contributing pair with T_k > 0.5 (strict):
+        median = depth[m] — a copy, not an interpolation, NOT multiplied by alpha;   index = m's row in the call's arrays
+    and median = 0, index = -1 where the pixel has no contributing pair.  Where the transmittance crosses 1/2, m is the layer
+    that crosses it; where it never does, the pixel's last contributing layer.  The walk of a tile stops once none of its pixels
+    is above 1/2, which moves no bit.  `index` is what `blend_median_backward` takes back."""
+    start, end, mean_f, vinv, op = _params(startpoint, endpoint, mean, variance_inverse, opacity)
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    z, _ = _depth_args(depth, None, n, dev)
+    lib = _lib.load()
+    shape = (bins.height + 1, bins.width + 1)
+    median = torch.empty(shape, dtype=torch.float32, device=dev)
+    index = torch.empty(shape, dtype=torch.int32, device=dev)
+    # bins without a single entry have no tile list to point at: no pixel has a pair, which is the call without Gaussians
+    n_walk = n if bins.tile_list.numel() else 0
+    with torch.cuda.device(dev):
+        _lib.check(
+            lib.gcp_blend_median_forward(start.data_ptr(), end.data_ptr(), mean_f.data_ptr(), vinv.data_ptr(), op.data_ptr(),
+                                         z.data_ptr(), n_walk, bins.width, bins.height, bins.tile_start.data_ptr(),
+                                         bins.tile_list.data_ptr(), median.data_ptr(), index.data_ptr(), _stream(dev)),
+            "gcp_blend_median_forward",
+        )
+    return median, index
+
+
+def blend_median_backward(bins, startpoint, endpoint, index, grad_median):
+    """Backward of `blend_median_forward` for the loss <median, grad_median> (gcp_blend_median_backward) -> grad_depth f32[N]:
+        dL/dz_g = sum_{p : index(p) = g} grad_median(p)
+    — the median is piecewise constant in everything else: mean, variance_inverse and opacity get nothing.  `index`: what the
+    forward returned for the same bins.  0 for a Gaussian no pixel picked, and for one that capture-safe bins (`capacity=`) did
+    not list.  Summed per tile in pixel order, then per Gaussian over its tiles in order: no atomics, two calls give the same bits."""
+    start = _dev_tensor(startpoint, "startpoint", torch.int32, (2,))
+    end = _dev_tensor(endpoint, "endpoint", torch.int32, (2,))
+    dev = start.device
+    n = bins.n_gauss
+    _require(start.size(0) == n, f"startpoint: {start.size(0)} rows, the bins were built for {n}")
+    _require(end.size(0) == n and end.device == dev, f"endpoint: expected {n} rows on {dev}")
+    shape = (bins.height + 1, bins.width + 1)
+    idx = _dev_tensor(index, "index", torch.int32)
+    g = _dev_tensor(grad_median, "grad_median", torch.float32)
+    for t, name in ((idx, "index"), (g, "grad_median")):
+        _require(tuple(t.shape) == shape and t.device == dev, f"{name}: expected shape {shape} on {dev}")
+    lib = _lib.load()
+    grad_depth = torch.empty(n, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_blend_median_backward_workspace_bytes(bins.tile_capacity), dtype=torch.uint8, device=dev)
+        _lib.check(
+            lib.gcp_blend_median_backward(start.data_ptr(), end.data_ptr(), n, bins.width, bins.height, bins.tile_off.data_ptr(),
+                                          bins.tile_capacity, bins.tile_start.data_ptr(), idx.data_ptr(), g.data_ptr(),
+                                          grad_depth.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            "gcp_blend_median_backward",
+        )
+    return grad_depth
 
 
 def exclusive_scan_i32(x):
