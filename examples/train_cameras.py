@@ -52,6 +52,9 @@ simplegaussiansplat_tk71_amd.gs_model.GS_model_with_param.  Two data sources:
     python examples/train_cameras.py --test-every 8 --eval-every 100 --eval-json eval.json
                                                              # hold out every 8th camera (sorted by name, the llffhold convention),
                                                              # report PSNR / SSIM / L1 on them every 100 iterations and at the end
+    python examples/train_cameras.py --colmap DIR --init-scale knn
+                                                             # the initial scales from the exact nearest neighbours of the HIP
+                                                             # kernel (3dgs: upstream's rule) instead of torch.cdist + topk
 
 The reference's own checkout cannot be trained on: its images.bin (camera poses) is missing, so the synthetic
 scene renders its target images from a hidden set of Gaussians seen by a ring of cameras and then fits a
@@ -70,6 +73,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from simplegaussiansplat_tk71_amd import gs_model as gm  # noqa: E402
 from simplegaussiansplat_tk71_amd.synthetic import ring_cameras  # noqa: E402
+
+INIT_SCALES = ("cdist", "knn", "3dgs")  # --init-scale
 
 
 def synthetic_scene(n_gauss, n_cam, width, height, seed, device, with_alpha=False):
@@ -129,7 +134,7 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
           screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
           exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000, save_mesh=None, mesh_resolution=256,
-          mesh_trunc=None, normal_depth="expected", mesh_depth="expected"):
+          mesh_trunc=None, normal_depth="expected", mesh_depth="expected", init_scale="cdist"):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -200,6 +205,11 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     (`model.render(median=True)` through `gs_model.median_as_depth`; `model.extract_mesh(depth="median")`) instead of the
     expected depth — 2DGS's depth_ratio = 1 for bounded scenes, a pointer and not a tuned choice.  With "expected" (the
     default) no step and no output changes.
+    `init_scale`: where the initial scales come from.  "cdist" (the default): `gs_model.mean_neighbour_distance(neighbours,
+    start)`, the reference's torch.cdist + topk — quadratic in the cloud, and cancelled where the cloud lies far from its origin.
+    "knn": the same definition from the exact neighbours of the HIP kernel (`gs_model.neighbour_scale(start, "reference",
+    neighbours)`).  "3dgs": upstream 3DGS's rule, the root of the mean of the 3 smallest squared distances (`neighbours` is
+    ignored).  With "cdist" no step changes.
     Evaluation touches no gradient, statistic, optimiser state or generator.  LPIPS is not reported: it needs pretrained
     network weights.  The return value stays (model, losses)."""
     if adam not in gm.ADAM_MODES:
@@ -208,6 +218,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
         raise ValueError(f"densify: 'reference', 'device' or 'mcmc', got {densify!r}")
     if prune_on not in ("max", "sum"):
         raise ValueError(f"prune_on: 'max' or 'sum', got {prune_on!r}")
+    if init_scale not in INIT_SCALES:
+        raise ValueError(f"init_scale: 'cdist', 'knn' or '3dgs', got {init_scale!r}")
     if isinstance(background, str) and background != "random":
         raise ValueError(f"background: None, (r, g, b) or 'random', got {background!r}")
     dev = start.device
@@ -253,7 +265,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     n = start.shape[0]
     q = torch.zeros((n, 4), device=dev)
     q[:, 3] = 1  # identity rotation, (x, y, z, w) (gs_control.py:113-114)
-    scale = torch.log(gm.mean_neighbour_distance(neighbours, start))
+    if init_scale == "cdist":
+        scale = torch.log(gm.mean_neighbour_distance(neighbours, start))
+    else:
+        scale = torch.log(gm.neighbour_scale(start, "reference" if init_scale == "knn" else "3dgs", neighbours))
     opacity = torch.full((n, 1), math.log(opacity_init / (1 - opacity_init)), device=dev)
     sh = {"sh_frame": sh_frame, "active_sh_degree": 0 if sh_every else None, "centres": centres, "cov_dilation": dilation,
           "clamp_colour": clamp_colour}
@@ -486,6 +501,10 @@ def build_parser():
     ap.add_argument("--mesh-depth", choices=("expected", "median"), default="expected",
                     help="with --save-mesh: the depth map that is fused, as for --normal-depth (2DGS's depth_ratio = 1 fuses the "
                          "median depth of bounded scenes: a pointer, not a tuned choice)")
+    ap.add_argument("--init-scale", choices=INIT_SCALES, default="cdist",
+                    help="the initial scales: cdist = the reference's torch.cdist + topk (quadratic, cancelled far from the origin); "
+                         "knn = the same definition from the exact nearest neighbours of the HIP kernel; 3dgs = upstream 3DGS's "
+                         "root of the mean of the 3 smallest squared distances")
     ap.add_argument("--save-mesh", default=None, metavar="PATH",
                     help="after the last step: fuse the training cameras' depth maps into a TSDF volume and write its surface as a "
                          "triangle mesh .ply (rank 0); what --normal-reg and --distortion-reg shape the depth for")
@@ -537,7 +556,7 @@ if __name__ == "__main__":
                       filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
                       exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure, normal_reg=a.normal_reg,
                       normal_from=a.normal_from, save_mesh=a.save_mesh, mesh_resolution=a.mesh_resolution, mesh_trunc=a.mesh_trunc,
-                      normal_depth=a.normal_depth, mesh_depth=a.mesh_depth)
+                      normal_depth=a.normal_depth, mesh_depth=a.mesh_depth, init_scale=a.init_scale)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

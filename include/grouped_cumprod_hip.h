@@ -1131,6 +1131,29 @@ int gcp_mesh_write(const float* tsdf, const float* rgb, int32_t nx, int32_t ny, 
                    float voxel, float iso, const void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_faces, float* vertices,
                    int32_t* faces, float* colours, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours inside one cloud (gcp_knn.hip): what the initial scale of every Gaussian is made of (upstream
+ * 3DGS: simple-knn's distCUDA2; the reference: uitility.py:68-78 `kyori2`, torch.cdist + topk in batches).
+ *
+ * The definition.  xyz f32[n][3], FINITE coordinates (a precondition: with a NaN or an infinity the call still ends and
+ * still writes every word, but what it writes is not defined).  For points i != j
+ *     d2(i, j) = (dx * dx + dy * dy) + dz * dz,   dx = x_i - x_j ...   in float32, in that association, nothing fused
+ * — direct differences, not |a|^2 + |b|^2 - 2 a.b, so a cloud far from its origin loses nothing.  Row i of the outputs lists
+ * the k smallest pairs (d2(i, j), j) over all j != i, ascending, lexicographic: among equal distances the lower index comes
+ * first.  "Other" is by INDEX: a duplicate of point i at distance 0 is a neighbour, point i itself is not.
+ *     index int32[n][k]   j, in the caller's numbering
+ *     dist2 f32[n][k]     d2(i, j)
+ * A row with fewer than k other points (n <= k) is padded with index = -1, dist2 = +inf.  Every word of both outputs is
+ * written.  1 <= k <= 16, n < 2^31 - 1.
+ * The result is a function of xyz and k alone — the same bits whatever the spatial order of the points, the stream or the
+ * workspace's earlier contents; exact, not approximate (Morton order + two levels of exact boxes; pruning only on a float32
+ * bound that is strictly greater than the current k-th best).  No atomics, no allocation, no device->host read: capturable.
+ * ws: gcp_knn_workspace_bytes(n) bytes, any alignment.
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: n < 0 or too large, k outside 1..16, and with n > 0 a NULL xyz, index, dist2
+ * or ws; GCP_ERR_WORKSPACE: ws too small.  n == 0 is a no-op. */
+size_t gcp_knn_workspace_bytes(int64_t n);
+int gcp_knn(const float* xyz, int64_t n, int32_t k, int32_t* index, float* dist2, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,9 @@ SIGNATURES = {
     "gcp_mesh_count": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32, ctypes.c_float, _c_void_p, _sz, ctypes.POINTER(_i64), _c_void_p]),
     "gcp_mesh_write": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32] + [ctypes.c_float] * 5 + [_c_void_p, _sz, _i64, _i64]
                        + [_c_void_p] * 4),
+    # exact k nearest neighbours inside one cloud (gcp_knn.hip): xyz, n, k -> index i32[n,k], dist2 f32[n,k]; ws, ws_bytes, stream
+    "gcp_knn_workspace_bytes": (_sz, [_i64]),
+    "gcp_knn": (ctypes.c_int, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _sz, _c_void_p]),
 }
 
 ABI_VERSION = 4

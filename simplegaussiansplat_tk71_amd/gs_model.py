@@ -11,7 +11,8 @@ the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`)
 (density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
 `apply_filter`), the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`) and the
 normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`, `median_as_depth`) and the mesh extraction
-(mesh.py: `TSDFVolume`, `extract_surface`).
+(mesh.py: `TSDFVolume`, `extract_surface`) and the exact nearest neighbours for the initial scales (knn.py: `nearest_neighbours`,
+`neighbour_scale`).
 Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
     channels (gs_model.py:454, SURVEY.md §0 Q6) — `reference_layout=True` reproduces that;
@@ -32,6 +33,7 @@ from .cuda_kernel import paint_maps as _paint_maps
 from .density import DENSIFY_ON, SCREEN_GRADS, accumulate_screen_grads
 from .exposure import CameraExposure
 from .filter3d import apply_filter, filter_from_rate, sampling_rate
+from .knn import nearest_neighbours, neighbour_scale
 from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
 from .mesh import TSDFVolume, extract_surface
@@ -67,6 +69,8 @@ __all__ = [
     "get_expon_lr_func",
     "mean_neighbour_distance",
     "median_as_depth",
+    "nearest_neighbours",
+    "neighbour_scale",
     "normal_consistency",
     "normal_consistency_map",
     "sampling_rate",
