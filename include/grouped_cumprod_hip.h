@@ -119,13 +119,36 @@ int gcp_cumsum_forward(const float* x, const int32_t* key, float* y, int64_t n,
  * `inv` instead; `inv_len` is never read outside [0, n_groups).  So a call with
  * `inv` = any key with the right runs and a one-entry dummy `inv_len` is still
  * served, at the old cost.  The reference's O(sum L^2) per-element loop is
- * replaced by one O(n) reverse segmented scan.  Traffic: 16 B / element plus
- * ~4 B per group (20 B / element on ranges that fall back to `inv`).
+ * replaced by one O(n) reverse segmented scan.
+ * `param_cumprod` must be the inclusive grouped product of `param` over the
+ * same groups, that is gcp_cumprod_forward's output for (`param`, `inv`): what
+ * the reference's callers pass.  The kernel does not stream it: every
+ * 1024-element range rebuilds its part from `param` (a differently associated
+ * fp32 product, so grad_in agrees with gcp_cumprod_backward_given to rounding,
+ * not bit for bit) and reads the given array only for one anchor element below
+ * the range and for the look-back behind a 4096-element tile.  Which elements
+ * are read depends on positions and data alone: results are deterministic.
+ * Traffic: 12 B / element (param, grad_out in; grad_in out) plus anchors and
+ * look-back (~0.3 B / element) and ~4 B per group (16 B / element on ranges
+ * that fall back to `inv`).
  */
 int gcp_cumprod_backward(const float* param, const float* param_cumprod,
                          const float* grad_out, const int32_t* inv, float* grad_in,
                          const int32_t* inv_len, int64_t n, int64_t n_groups,
                          void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * The same sum with every factor taken from the GIVEN `param_cumprod`, which
+ * may then be any array: the sum is linear in it, so the plain product times
+ * a per-group factor (what gcp_cumprod_forward_carry produces) gives that
+ * factor times the plain result.  Same operands and rules as
+ * gcp_cumprod_backward.  Traffic: 16 B / element plus ~4 B per group (20 B /
+ * element on ranges that fall back to `inv`).
+ */
+int gcp_cumprod_backward_given(const float* param, const float* param_cumprod,
+                               const float* grad_out, const int32_t* inv, float* grad_in,
+                               const int32_t* inv_len, int64_t n, int64_t n_groups,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Suffix form of gcp_cumsum_forward: y[i] = sum of x[k] over k >= i in the same

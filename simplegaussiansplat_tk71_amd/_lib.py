@@ -36,6 +36,10 @@ SIGNATURES = {
         ctypes.c_int,
         [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _c_void_p, _sz, _c_void_p],
     ),
+    "gcp_cumprod_backward_given": (
+        ctypes.c_int,
+        [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _i64, _c_void_p, _sz, _c_void_p],
+    ),
     "gcp_check_groups": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.POINTER(_i64), _c_void_p]),
     "gcp_check_permutation": (ctypes.c_int, [_c_void_p, _i64, ctypes.POINTER(_i64), _c_void_p]),
     "gcp_check_group_ids": (ctypes.c_int, [_c_void_p, _i64, _i64, ctypes.POINTER(_i64), _c_void_p]),

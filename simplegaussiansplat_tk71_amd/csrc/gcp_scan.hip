@@ -43,6 +43,11 @@
 //     store: one O(n) pass.  Its head flags come from the group ends `inv_len`
 //     (a few entries per wave) instead of per-element `inv`: 16 B / element
 //     (param, cumprod, grad_out, grad_in), 20 B where a wave falls back to `inv`.
+//     That is MODE 2, gcp_cumprod_backward_given.  gcp_cumprod_backward (MODE 4)
+//     does not stream cumprod either: it is a function of param and the groups,
+//     which the tile holds, so every wave rebuilds its 1024 elements of it with a
+//     second segmented scan (a product, in ascending address order) continued
+//     from one given element below its range: 12 B / element.
 //
 // HBM-bound by construction (12 B or 16 B per element, ~10 VALU per element):
 // no MFMA.  All index arithmetic on the array is 64-bit.
@@ -70,7 +75,7 @@ using namespace gcp;
 typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef int int4_t __attribute__((ext_vector_type(4)));
 
-enum : int { M_CUMPROD_FWD = 0, M_CUMSUM_FWD = 1, M_CUMPROD_BWD = 2, M_CUMSUM_REV = 3 };
+enum : int { M_CUMPROD_FWD = 0, M_CUMSUM_FWD = 1, M_CUMPROD_BWD = 2, M_CUMSUM_REV = 3, M_CUMPROD_BWD_RECOMPUTE = 4 };
 
 constexpr int kThreads = 256;      // 4 waves
 constexpr int kWaves = 4;
@@ -110,8 +115,10 @@ static_assert((kLbChunks - 1) % kLbBatchBwd == 0, "chunks after the first are fe
 template <int MODE>
 struct Mode {
   static constexpr bool kMul = (MODE == M_CUMPROD_FWD);
-  static constexpr bool kRev = (MODE == M_CUMPROD_BWD || MODE == M_CUMSUM_REV);
-  static constexpr bool kBwd = (MODE == M_CUMPROD_BWD);
+  static constexpr bool kRev = (MODE == M_CUMPROD_BWD || MODE == M_CUMSUM_REV || MODE == M_CUMPROD_BWD_RECOMPUTE);
+  static constexpr bool kBwd = (MODE == M_CUMPROD_BWD || MODE == M_CUMPROD_BWD_RECOMPUTE);
+  // the backward whose tile does not load param_cumprod: it rebuilds the tile's part of it from param (scan_tile, "in-tile y")
+  static constexpr bool kRecompute = (MODE == M_CUMPROD_BWD_RECOMPUTE);
   static constexpr int kBatch = kBwd ? kLbBatchBwd : kLbBatch;  // chunks are processed one by one in the same order either way
 };
 
@@ -156,6 +163,23 @@ __device__ __forceinline__ float wave_seg_scan(float v, int h, int lane) {
   t = dpp_f<0x142, 0xa>(id, v); v = M::op(v, ((lane & 48) - 1 >= h) ? t : id);
   // lane 31 -> rows 2,3
   t = dpp_f<0x143, 0xc>(id, v); v = M::op(v, (31 >= h) ? t : id);
+  return v;
+}
+
+// The mirror image, products only: lane l takes lanes l .. hp, where `hp` = nearest lane >= this one that starts a
+// segment (64 if none), so lane l may absorb lane s iff s <= hp.  DPP has no broadcast towards lower lanes: row_shl
+// 1/2/4/8 inside the rows of 16, then the rows chain downwards through three wave-uniform hand-overs (lanes 48, 32, 16).
+__device__ __forceinline__ float wave_seg_scan_down_mul(float v, int hp, int lane) {
+  float t;
+  t = dpp_f<0x101, 0xf>(1.0f, v); v = v * ((lane + 1 <= hp) ? t : 1.0f);
+  t = dpp_f<0x102, 0xf>(1.0f, v); v = v * ((lane + 2 <= hp) ? t : 1.0f);
+  t = dpp_f<0x104, 0xf>(1.0f, v); v = v * ((lane + 4 <= hp) ? t : 1.0f);
+  t = dpp_f<0x108, 0xf>(1.0f, v); v = v * ((lane + 8 <= hp) ? t : 1.0f);
+#pragma unroll
+  for (int q = 2; q >= 0; --q) {
+    const float c = readlane_f(v, 16 * (q + 1));
+    v = v * (((lane >> 4) == q && hp >= 16 * (q + 1)) ? c : 1.0f);
+  }
   return v;
 }
 
@@ -298,10 +322,11 @@ __device__ __forceinline__ void wave_sync_lds() {
 
 // Fills `bits` (bit i: element wlo + i is the last of its group) and returns true when the ends describe the wave's
 // range: 0 <= ga <= gb < n_groups, start(ga) <= wlo < end(ga), start(gb) <= whi < end(gb), the ends of ga-1 .. gb
-// strictly increasing.  `gend` = end(gb), the exclusive end of the group the wave's first element (scan order) is in.
+// strictly increasing.  `gend` = end(gb), the exclusive end of the group the wave's first element (scan order) is in;
+// `gstart` = start(ga), the first element of the group that wlo is in.
 // Every `ends` index read lies in [ga - 1, gb] and so in [0, n_groups), whatever `inv` holds.
 __device__ __forceinline__ bool group_ends(const ScanArgs& a, unsigned* bits, i64 wlo, i64 whi, int ga, int gb, int lane,
-                                          i64& gend) {
+                                          i64& gend, i64& gstart) {
   if (lane < kBitWords) bits[lane] = 0u;
   wave_sync_lds();
   if (!(wlo <= whi && ga >= 0 && ga <= gb && (i64)gb < a.n_groups && (i64)gb - ga + 2 <= 64 * kEndIters)) return false;
@@ -315,6 +340,7 @@ __device__ __forceinline__ bool group_ends(const ScanArgs& a, unsigned* bits, i6
   }
   bool bad = false;
   gend = 0;
+  gstart = (i64)__builtin_amdgcn_readlane(e[0], 0);
 #pragma unroll
   for (int it = 0; it < kEndIters; ++it) {
     const int j = it * 64 + lane;
@@ -343,6 +369,7 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   typedef Mode<MODE> MD;
   constexpr bool REV = MD::kRev;
   constexpr bool BWD = MD::kBwd;
+  constexpr bool RECOMP = MD::kRecompute;
   typedef Monoid<MD::kMul> M;
   const float id = M::identity();
   constexpr int WT = 256 * kRows;  // elements per wave
@@ -393,7 +420,9 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     if constexpr (!BWD) load_keys(r);
     if (FULL) {
       if (nt_main) {  // wave-uniform
-        if constexpr (BWD) {
+        if constexpr (RECOMP) {  // grad_out alone: its factor is rebuilt from param below ("in-tile y")
+          v[r] = ld4<ALIGNED, true>(a.in2 + p0[r]);
+        } else if constexpr (BWD) {
           v[r] = ld4<ALIGNED, true>(a.in2 + p0[r]) * ld4<ALIGNED, true>(a.in1 + p0[r]);
         } else if constexpr (INDEXED) {
           v[r] = ld4_indexed<ALIGNED, true>(a.in0, a.index, p0[r], ix[r]);
@@ -401,7 +430,9 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
           v[r] = ld4<ALIGNED, true>(a.in0 + p0[r]);
         }
       } else {
-        if constexpr (BWD) {
+        if constexpr (RECOMP) {
+          v[r] = ld4<ALIGNED>(a.in2 + p0[r]);
+        } else if constexpr (BWD) {
           v[r] = ld4<ALIGNED>(a.in2 + p0[r]) * ld4<ALIGNED>(a.in1 + p0[r]);
         } else if constexpr (INDEXED) {
           v[r] = ld4_indexed<ALIGNED, false>(a.in0, a.index, p0[r], ix[r]);
@@ -411,7 +442,10 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
       }
       if constexpr (BWD) xp[r] = ld4<ALIGNED, true>(a.in0 + p0[r]);  // param is never re-read by a look-back
     } else {
-      if constexpr (BWD) {
+      if constexpr (RECOMP) {
+        v[r] = ld4_guard(a.in2, p0[r], n, 0.0f);
+        xp[r] = ld4_guard(a.in0, p0[r], n, 1.0f);
+      } else if constexpr (BWD) {
         const float4_t g = ld4_guard(a.in2, p0[r], n, 0.0f);
         const float4_t c = ld4_guard(a.in1, p0[r], n, 0.0f);
         xp[r] = ld4_guard(a.in0, p0[r], n, 1.0f);
@@ -431,6 +465,11 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   // the wave a whole round trip with nothing of its own in flight; behind, that round trip overlaps the data's.
   if constexpr (BWD) {
     if (wlo <= whi) { ga = a.key[wlo]; gb = a.key[whi]; }
+  }
+  // in-tile y: the one float of the given param_cumprod a group that enters the wave's range from below continues from
+  float anchor = 1.0f;
+  if constexpr (RECOMP) {
+    if (wlo > 0 && wlo <= whi) anchor = a.in1[wlo - 1];
   }
 
   // key of the element just before this wave's chunk in scan order
@@ -471,13 +510,18 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   bool from_ends = false;
   i64 gend = 0;  // end of the group of the wave's first element (scan order): the look-back's membership bound
   unsigned* const wbits = s_bits + kBitWords * wu;
+  i64 gstart = 0;  // start of the group the wave's lowest element is in (from the ends)
+  int kbelow = 0;  // ... or the key of the element below it (from the keys)
   if constexpr (BWD) {
-    from_ends = group_ends(a, wbits, wlo, whi, ga, gb, lane, gend);
+    from_ends = group_ends(a, wbits, wlo, whi, ga, gb, lane, gend, gstart);
     if (!from_ends) {
 #pragma unroll
       for (int r = 0; r < kRows; ++r) load_keys(r);
       if (nb_exists) nbk = a.key[pn];
       if (do_lb) lbk = ld4_guard(a.key, lbp, n, 0);
+      if constexpr (RECOMP) {
+        if (wlo > 0 && wlo <= whi) kbelow = a.key[wlo - 1];
+      }
     }
   }
 
@@ -489,6 +533,66 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
   unsigned openbits = 0;  // bit 4r+k: no head among items 0..k of row r in this lane
   unsigned lanes_open = 0;  // bit r: no head in lanes [0, lane) of row r
 
+  // ---- in-tile y (MODE 4): param_cumprod of the wave's own 1024 elements, rebuilt from param ---------------------------
+  // A segmented PRODUCT scan in ascending address order, against the direction of everything else here: element p
+  // starts a group iff element p - 1 ends one, so its head flags are the sum scan's moved by one element.  In that
+  // order the wave's range runs from row kRows-1, lane 63 up to row 0, lane 0, and inside a lane from item 3 to item 0.
+  // A group that enters the range from below continues from `anchor`, the given y of the element below the range, so
+  // no wave waits for another wave's product; everything outside the wave's range (look-back, descriptors, follow-up
+  // kernel) reads the given y as in MODE 2.  v[] holds grad_out on entry and grad_out * y on exit: where MODE 2 starts.
+  unsigned ebits = 0;  // bit 4r+i: memory element p0[r] + i (scan item 3 - i) ends its group
+  if constexpr (RECOMP) {
+    unsigned long long e3[kRows];  // lanes whose highest element ends a group: the lane before them starts one at its lowest
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+      unsigned nib;
+      if (from_ends) {
+        const int off = WT - 4 - r * 256 - lane * 4;  // p0[r] - wlo
+        nib = (wbits[off >> 5] >> (off & 31)) & 0xfu;
+      } else {
+        const int up = (r == 0) ? nbk : __builtin_amdgcn_readlane(kk[r > 0 ? r - 1 : 0].w, 63);
+        const int pk = dpp_i<0x138, 0xf>(up, kk[r].w);  // key of element p0[r] + 4
+        nib = (unsigned)(kk[r].w != kk[r].z) | ((unsigned)(kk[r].z != kk[r].y) << 1) | ((unsigned)(kk[r].y != kk[r].x) << 2) |
+              ((unsigned)(kk[r].x != pk) << 3);
+      }
+      if (FULL) {  // the last element of the array ends a group whatever the operands say
+        if ((lt == 0) && (w == 0) && (r == 0) && (lane == 0)) nib |= 8u;
+      } else {     // ... and nothing behind it does
+        const i64 m = n - p0[r];  // elements of this vector inside the array
+        nib = (m >= 4) ? (m == 4 ? (nib | 8u) : nib) : (m <= 0 ? 0u : ((nib | (1u << (m - 1))) & ((1u << m) - 1u)));
+      }
+      ebits |= nib << (4 * r);
+      e3[r] = __ballot((nib & 8u) != 0u);
+    }
+    // the range's lowest element starts a group (then the anchor is not used)
+    const bool low_head = (wlo == 0) || (from_ends ? (gstart == wlo) : (kbelow != ga));
+    float C = anchor;  // product entering the row from below (wave-uniform)
+#pragma unroll
+    for (int r = kRows - 1; r >= 0; --r) {
+      // F_i: memory element p0[r] + i starts a group (scan item 3 - i; xp[r] is in scan order: .w is the lowest address)
+      const bool below = (r == kRows - 1) ? low_head : ((e3[r < kRows - 1 ? r + 1 : r] & 1ull) != 0ull);
+      const bool F0 = (lane == 63) ? below : (((e3[r] >> 1) >> lane) & 1ull) != 0ull;
+      const bool F1 = (ebits >> (4 * r)) & 1u, F2 = (ebits >> (4 * r + 1)) & 1u, F3 = (ebits >> (4 * r + 2)) & 1u;
+      const float q0 = xp[r].w;
+      const float q1 = F1 ? xp[r].z : q0 * xp[r].z;
+      const float q2 = F2 ? xp[r].y : q1 * xp[r].y;
+      const float q3 = F3 ? xp[r].x : q2 * xp[r].x;
+      const bool n0 = !F0, n1 = n0 && !F1, n2 = n1 && !F2, n3 = n2 && !F3;  // no group start among elements 0 .. i
+      const unsigned long long pm = __ballot(!n3);
+      const unsigned long long from = pm >> lane;
+      const int hp = from ? lane + __builtin_ctzll(from) : 64;
+      const float inc = wave_seg_scan_down_mul(q3, hp, lane);
+      const float ex = dpp_f<0x130, 0xf>(1.0f, inc);  // wave_shl:1: lane l <- lane l + 1, lane 63 keeps the identity
+      const float e = (((pm >> 1) >> lane) == 0ull) ? C * ex : ex;  // no start in the lanes before: the row's carry too
+      v[r].w *= n0 ? e * q0 : q0;
+      v[r].z *= n1 ? e * q1 : q1;
+      v[r].y *= n2 ? e * q2 : q2;
+      v[r].x *= n3 ? e * q3 : q3;
+      const float tot = readlane_f(inc, 0);
+      C = pm ? tot : C * tot;
+    }
+  }
+
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     // previous key in scan order for item 0
@@ -498,7 +602,9 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
     const int pk = dpp_i<0x138, 0xf>(lane0_prev, kk[r].w);  // wave_shr:1, lane 0 keeps old
 
     bool f0, f1, f2, f3;
-    if (BWD && from_ends) {
+    if constexpr (RECOMP) {
+      f0 = (ebits >> (4 * r + 3)) & 1u; f1 = (ebits >> (4 * r + 2)) & 1u; f2 = (ebits >> (4 * r + 1)) & 1u; f3 = (ebits >> (4 * r)) & 1u;
+    } else if (BWD && from_ends) {
       // bit i of the nibble: memory element p0[r] + i ends its group; scan item k is memory element p0[r] + 3 - k
       const int off = WT - 4 - r * 256 - lane * 4;  // p0[r] - wlo
       const unsigned nib = (wbits[off >> 5] >> (off & 31)) & 0xfu;
@@ -840,7 +946,8 @@ __device__ __forceinline__ void scan_tile(const ScanArgs& a, const i64 lt, float
 // resident_tiles_lds() below (profiles/r24_fwd_occupancy.md).  The cumprod backward holds
 // three arrays per element: four blocks per CU (<= 128 VGPRs, no scratch: tests/test_bwd_occupancy.py), so that a tile
 // waiting for its group ends leaves three others' loads in flight and not two (cfg3: 457 -> 436 us; a launch whose waves ALL
-// take the key fall-back pays 2-3 % for it: profiles/r08_bwd_occupancy.md).  The reverse sum, the indexed and the
+// take the key fall-back pays 2-3 % for it: profiles/r08_bwd_occupancy.md).  The backward that rebuilds y (MODE 4) holds two
+// arrays and a second scan: 125 VGPRs, the same four blocks (tests/test_bwd_recompute_listing.py).  The reverse sum, the indexed and the
 // in-place scans are left to the register allocator (the reverse sum: 105-107 VGPRs, four blocks per CU, its best step).
 template <int MODE>
 constexpr int waves_per_simd(bool indexed, bool inplace, bool upper) {
@@ -1468,6 +1575,14 @@ int gcp_cumsum_reverse_carry(const float* x, const int32_t* inv, const float* ca
 int gcp_cumprod_backward(const float* param, const float* param_cumprod, const float* grad_out,
                          const int32_t* inv, float* grad_in, const int32_t* inv_len, int64_t n,
                          int64_t n_groups, void* ws, size_t ws_bytes, void* stream) {
+  if (n > 0 && (!inv_len || n_groups <= 0)) return GCP_ERR_INVALID_ARGUMENT;
+  return launch_scan<M_CUMPROD_BWD_RECOMPUTE>(param, param_cumprod, grad_out, inv, grad_in, n, ws, ws_bytes,
+                                              stream, nullptr, nullptr, inv_len, n_groups);
+}
+
+int gcp_cumprod_backward_given(const float* param, const float* param_cumprod, const float* grad_out,
+                               const int32_t* inv, float* grad_in, const int32_t* inv_len, int64_t n,
+                               int64_t n_groups, void* ws, size_t ws_bytes, void* stream) {
   if (n > 0 && (!inv_len || n_groups <= 0)) return GCP_ERR_INVALID_ARGUMENT;
   return launch_scan<M_CUMPROD_BWD>(param, param_cumprod, grad_out, inv, grad_in, n, ws, ws_bytes,
                                     stream, nullptr, nullptr, inv_len, n_groups);

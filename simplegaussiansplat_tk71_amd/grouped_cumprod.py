@@ -242,12 +242,17 @@ def grouped_cumsum_reverse_carry(x, inv, carry, out):
     _forward_carry("gcp_cumsum_reverse_carry", x, inv, carry, out)
 
 
-def grouped_cumprod_backward(param, param_cumprod, grad_out, inv, grad_in, inv_len, *, workspace=None):
+def grouped_cumprod_backward(param, param_cumprod, grad_out, inv, grad_in, inv_len, *, workspace=None, given=False):
     """grad_in[j] = sum_{i=j}^{inv_len[inv[j]]-1} grad_out[i] * param_cumprod[i] / p'_j.
 
     reference: cuda_kernel/grouped_cumprod_backward.cu:9-65 (p'_j = param[j] or 1e-8
     when it is 0, :25).  `inv` = dense group id per element, `inv_len` = exclusive
     end offset per group (cuda_test.py:27).
+
+    `param_cumprod` is grouped_cumprod_forward's output for (`param`, `inv`): the kernel
+    rebuilds most of it from `param` instead of streaming it (12 B / element, not 16).
+    given=True takes every factor from the array as passed, whatever it holds (e.g. the
+    forward_carry product, a per-group multiple of the plain one).
     """
     _require(isinstance(param, torch.Tensor), "param: expected a torch.Tensor")
     n = param.numel()  # reference: n = param.numel() (grouped_cumprod_backward.cu:52)
@@ -264,7 +269,7 @@ def grouped_cumprod_backward(param, param_cumprod, grad_out, inv, grad_in, inv_l
     _no_alias(grad_in, "grad_in", (param, "param"), (param_cumprod, "param_cumprod"), (grad_out, "grad_out"), (inv, "inv"),
               (inv_len, "inv_len"))
     _launch(
-        "gcp_cumprod_backward",
+        "gcp_cumprod_backward_given" if given else "gcp_cumprod_backward",
         dev,
         n,
         (param.data_ptr(), param_cumprod.data_ptr(), grad_out.data_ptr(), inv.data_ptr(), grad_in.data_ptr(),

@@ -41,7 +41,8 @@ def main():
         "ideal 16B (3R+1W)": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 0, st), 16),
         "ideal 16B nt-store": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 1, st), 16),
         "ideal 16B nt-ld+st": (lambda: lib.ceiling16(p.x.data_ptr(), y.data_ptr(), p.grad_out.data_ptr(), g.data_ptr(), m, 2, st), 16),
-        "cumprod_bwd": (lambda: gc.grouped_cumprod_backward(p.x, y, p.grad_out, p.inv, g, p.inv_len), 16),  # group ends from inv_len
+        "cumprod_bwd given y": (lambda: gc.grouped_cumprod_backward(p.x, y, p.grad_out, p.inv, g, p.inv_len, given=True), 16),  # group ends from inv_len
+        "cumprod_bwd": (lambda: gc.grouped_cumprod_backward(p.x, y, p.grad_out, p.inv, g, p.inv_len), 12),  # ... and y rebuilt in the tile
     }
     res = {k: [] for k in ops}
     for _ in range(3):
