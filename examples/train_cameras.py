@@ -134,7 +134,8 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
           prune_contribution=None, prune_at=(), prune_on="max", adam="tensor", test_every=0, eval_every=0, evals=None, names=None,
           screen_grad="signed", distortion_reg=0.0, distortion_from=0, filter_3d=False, filter_every=100, exposure=False,
           exposure_lr_init=0.01, exposure_lr_final=0.001, save_exposure=None, normal_reg=0.0, normal_from=7000, save_mesh=None, mesh_resolution=256,
-          mesh_trunc=None, normal_depth="expected", mesh_depth="expected", init_scale="cdist"):
+          mesh_trunc=None, normal_depth="expected", mesh_depth="expected", init_scale="cdist", mesh_keep=None, mesh_min_faces=None,
+          mesh_normals=False):
     """`world` > 1: one process per GPU under torch.distributed; every rank holds the whole scene, renders
     `batch[rank::world]` and the gradients are all-reduced (GS_model_with_param.allreduce_grads).
     `background`: None (black, the default), a fixed (r, g, b), or "random" — a new colour per step (drawn from torch's
@@ -201,6 +202,10 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     `ply_io.save_mesh`; `batch_size` cameras at a time; a running mean is order-dependent, so the ranks do not share the work).
     `mesh_resolution` = 256 and the default truncation of 5 voxels are pointers from 2DGS's usage, not tuned here.  With
     save_mesh=None (the default) no step and no output changes.
+    `mesh_keep` / `mesh_min_faces`: with either given (the other then defaults to 50) the mesh is cleaned before it is written:
+    `model.extract_mesh(keep_largest=, min_faces=)`, 2DGS's post_process_mesh rule — 50 / 50 are its values, pointers and not
+    tuned here.  `mesh_normals`: the file carries `mesh.vertex_normals` of what is written (`nx ny nz`).  All three are ignored
+    without save_mesh; with none of them the file is what it was.
     `normal_depth` / `mesh_depth` "median": the depth surface of the normal term / the fused depth is the median depth map
     (`model.render(median=True)` through `gs_model.median_as_depth`; `model.extract_mesh(depth="median")`) instead of the
     expected depth — 2DGS's depth_ratio = 1 for bounded scenes, a pointer and not a tuned choice.  With "expected" (the
@@ -413,9 +418,14 @@ def train(start, P, K, wh, targets, iterations=300, batch_size=3, loss_lamda=0.2
     if save_mesh is not None and rank == 0:
         from simplegaussiansplat_tk71_amd import ply_io
 
-        vertices, faces, colours = model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc, batch_size=batch_size,
-                                                      **({"depth": "median"} if mesh_depth == "median" else {}))
-        ply_io.save_mesh(save_mesh, vertices, faces, colours)
+        options = {"depth": "median"} if mesh_depth == "median" else {}
+        if mesh_keep is not None or mesh_min_faces is not None:
+            options.update(keep_largest=mesh_keep, min_faces=mesh_min_faces)
+        if mesh_normals:
+            options["normals"] = True
+        vertices, faces, colours, *normals = model.extract_mesh(P, K, wh, resolution=mesh_resolution, trunc=mesh_trunc, batch_size=batch_size,
+                                                                **options)
+        ply_io.save_mesh(save_mesh, vertices, faces, colours, *normals)
         log(f"mesh: {vertices.shape[0]} vertices, {faces.shape[0]} faces -> {save_mesh}")
     return model, losses
 
@@ -512,6 +522,14 @@ def build_parser():
                     help="with --save-mesh: voxels along the scene cube's side (256: a pointer from 2DGS's usage, not tuned here)")
     ap.add_argument("--mesh-trunc", type=float, default=None, metavar="F",
                     help="with --save-mesh: the truncation distance in world units (default: 5 voxels; not tuned here)")
+    ap.add_argument("--mesh-keep", type=int, default=None, metavar="N",
+                    help="with --save-mesh: clean the mesh, keeping the N connected components with the most faces (ties all stay); "
+                         "if only --mesh-min-faces is given, 50: 2DGS's post_process_mesh value, a pointer and not tuned here")
+    ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="M",
+                    help="with --save-mesh: clean the mesh, dropping components of fewer than M faces; if only --mesh-keep is given, "
+                         "50: 2DGS's value, a pointer and not tuned here")
+    ap.add_argument("--mesh-normals", action="store_true",
+                    help="with --save-mesh: write area-weighted vertex normals (nx ny nz), computed after the cleaning")
     return ap
 
 
@@ -556,7 +574,8 @@ if __name__ == "__main__":
                       filter_3d=a.filter_3d, filter_every=a.filter_every, exposure=a.exposure, exposure_lr_init=a.exposure_lr_init,
                       exposure_lr_final=a.exposure_lr_final, save_exposure=a.save_exposure, normal_reg=a.normal_reg,
                       normal_from=a.normal_from, save_mesh=a.save_mesh, mesh_resolution=a.mesh_resolution, mesh_trunc=a.mesh_trunc,
-                      normal_depth=a.normal_depth, mesh_depth=a.mesh_depth, init_scale=a.init_scale)
+                      normal_depth=a.normal_depth, mesh_depth=a.mesh_depth, init_scale=a.init_scale,
+                      mesh_keep=a.mesh_keep, mesh_min_faces=a.mesh_min_faces, mesh_normals=a.mesh_normals)
     if a.eval_json and rank == 0:
         with open(a.eval_json, "w") as f:
             json.dump(evals, f, indent=1)

@@ -1154,6 +1154,66 @@ int gcp_mesh_write(const float* tsdf, const float* rgb, int32_t nx, int32_t ny, 
                    float voxel, float iso, const void* ws, size_t ws_bytes, int64_t n_vertices, int64_t n_faces, float* vertices,
                    int32_t* faces, float* colours, void* stream);
 
+/* ---- mesh cleaning and vertex normals (csrc/gcp_meshclean.hip): what 2DGS, GOF, RaDe-GS and PGSR do through Open3D's
+ * post_process_mesh after the fusion ----------------------------------------------------------------------------------------
+ * The mesh: faces int32[F][3] over V vertices, ANY indexed triangle list (unreferenced vertices, repeated faces, faces that name
+ * a vertex twice, ids in any order); 3 V and 3 F fit int32.  A face with an index outside [0, V) is never addressed through: every
+ * kernel tests the three indices first and skips the whole face.  Integer work, or float32 in a pinned order: every output is a
+ * function of the mesh alone, the same bits on every run.  No float atomic, no inter-block wait.
+ *
+ * gcp_mesh_components: two vertices belong together when a face names both — the shared-VERTEX rule.  (Open3D's
+ * cluster_connected_triangles joins triangles over a shared EDGE; the two differ only where shells touch in a single vertex,
+ * which the extraction above cannot produce: its output is a combinatorial manifold.)
+ *   label int32[V]   the SMALLEST vertex index of the vertex's component
+ *   size  int32[V]   at a component's label: the number of its faces (a face belongs to the component of its first vertex, which
+ *                    is that of all three); 0 in every other row
+ * Four launches: init; hook, one thread per face — a union-find in `label`, the larger root always hooked under the smaller with a
+ * compare-and-swap, root walks with path halving, no other loop and no wait; flatten, one thread per vertex; count, one thread
+ * per face, integer atomics aggregated per wave (it needs the final labels).  F = 0: the init alone.  V = 0: nothing.
+ * Faces with an index outside [0, V) are IGNORED here and reported: status_dev (device int32, may be NULL) receives 1 if there
+ * was one, else 0.  ws: gcp_mesh_components_workspace_bytes(V, F) bytes, 256-byte aligned.  No device->host read: capturable.
+ *
+ * gcp_mesh_select / gcp_mesh_compact: 2DGS's rule.  keep_largest = k >= 1, min_faces = m >= 1; c_k = the k-th largest component
+ * face count, or the smallest count if there are fewer than k components; T = max(c_k, m); a component is kept iff its count
+ * >= T.  Ties at the threshold are all kept: no tie-break, a function of the mesh alone.  A face is kept with its component, a
+ * vertex iff a kept face names it — unreferenced vertices go.  T is found on the device (gcp_sort_pairs_u32 of `size`).
+ *   gcp_mesh_select runs the components, the sort, the keep flags and two gcp_exclusive_scan_i32 into ws
+ *     (gcp_mesh_clean_workspace_bytes(V, F) bytes, 256-byte aligned) and writes the kept counts V', F' to totals_host[0..1] — ONE
+ *     host read of (status, V', F'), for which it synchronises the stream: NOT capturable.  GCP_ERR_INVALID_ARGUMENT from that
+ *     read when a face index lies outside [0, V).  V = 0 or F = 0: nothing is kept, nothing is launched, totals 0.
+ *   gcp_mesh_compact takes the same faces, V, F and the ws gcp_mesh_select filled, with V', F' as returned, and writes
+ *     vertices_out f32[V'][3], faces_out int32[F'][3] with renumbered indices and, where given, colours_out / normals_out
+ *     f32[V'][3] from colours / normals f32[V][3].  Vertices and faces keep their input order (by (owner, kind) and by (cell,
+ *     tetrahedron, triangle) for the extraction's); kept rows are bit copies; with everything kept the outputs are the inputs bit
+ *     for bit.  Outputs must not overlap inputs.  V' = F' = 0 launches nothing.
+ *
+ * gcp_mesh_vertex_normals: Open3D's compute_vertex_normals.  n_v = normalise(sum over the corners (f, j) that name v of
+ * (b - a) x (c - a), (a, b, c) the vertices of f) — un-normalised cross products, hence area-weighted; zero-area faces add
+ * nothing; a face counts once per corner that names v.  A zero or non-finite sum gives (0, 0, 0), never a NaN.  The extraction's
+ * faces are counter-clockwise seen from where the field grows, so these normals point OUT of the surface, towards the cameras.
+ * The order is pinned without atomics: the 3 F corners are stably sorted by vertex id (gcp_sort_pairs_u32, key_bits =
+ * bit length of V, at most 30: the corners of a face with a bad index carry the key V and are left out), run starts come from the
+ * sorted keys, one thread per vertex adds its faces in ascending corner index 3 f + j in float32, each cross product recomputed
+ * from the three positions (nothing fused), the sum scaled by a power of two before |.| so that no square overflows or vanishes.
+ * Every word of normals f32[V][3] is written.  ws: gcp_mesh_vertex_normals_workspace_bytes(V, F), 256-byte aligned.  No host
+ * read: capturable.
+ *
+ * GCP_ERR_INVALID_ARGUMENT before any HIP call: V or F negative, 3 V or 3 F past int32, k < 1 or m < 1, a NULL totals_host, a
+ * NULL pointer with work to do, V' > V or F' > F or negative, colours_out without colours, normals_out without normals.
+ * GCP_ERR_WORKSPACE: ws too small or misaligned.  The _workspace_bytes functions return 0 for refused sizes. */
+size_t gcp_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gcp_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* label, int32_t* size, int32_t* status_dev,
+                        void* ws, size_t ws_bytes, void* stream);
+size_t gcp_mesh_clean_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gcp_mesh_select(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int64_t keep_largest, int64_t min_faces, void* ws,
+                    size_t ws_bytes, int64_t* totals_host, void* stream);
+int gcp_mesh_compact(const int32_t* faces, int64_t n_faces, int64_t n_vertices, const float* vertices, const float* colours,
+                     const float* normals, const void* ws, size_t ws_bytes, int64_t n_vertices_out, int64_t n_faces_out, float* vertices_out,
+                     int32_t* faces_out, float* colours_out, float* normals_out, void* stream);
+size_t gcp_mesh_vertex_normals_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int gcp_mesh_vertex_normals(const float* vertices, const int32_t* faces, int64_t n_vertices, int64_t n_faces, float* normals, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Exact k nearest neighbours inside one cloud (gcp_knn.hip): what the initial scale of every Gaussian is made of (upstream
  * 3DGS: simple-knn's distCUDA2; the reference: uitility.py:68-78 `kyori2`, torch.cdist + topk in batches).

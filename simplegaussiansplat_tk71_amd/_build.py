@@ -15,7 +15,8 @@ ROOT = os.path.dirname(PKG_DIR)
 SRCS = [os.path.join(PKG_DIR, "csrc", f) for f in ("gcp_scan.hip", "gcp_bin.hip", "gcp_blend.hip", "gcp_sort.hip", "gcp_walk.hip", "gcp_compact.hip",
                                                     "gcp_pairs.hip", "gcp_pixels.hip", "gcp_project.hip", "gcp_splat.hip", "gcp_loss.hip", "gcp_optim.hip",
                                                     "gcp_densify.hip", "gcp_mcmc.hip", "gcp_contrib.hip", "gcp_absgrad.hip", "gcp_distort.hip", "gcp_filter3d.hip",
-                                                    "gcp_undistort.hip", "gcp_normal.hip", "gcp_tsdf.hip", "gcp_median.hip", "gcp_knn.hip")]
+                                                    "gcp_undistort.hip", "gcp_normal.hip", "gcp_tsdf.hip", "gcp_median.hip", "gcp_knn.hip",
+                                                    "gcp_meshclean.hip")]
 HDRS = [os.path.join(PKG_DIR, "csrc", f) for f in ("gcp_device.hpp", "gcp_tiles.hpp", "gcp_blend_shared.hpp", "gcp_project.hpp", "gcp_philox.hpp")]
 INCLUDE = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(PKG_DIR, "lib")

@@ -197,6 +197,17 @@ SIGNATURES = {
     "gcp_mesh_count": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32, ctypes.c_float, _c_void_p, _sz, ctypes.POINTER(_i64), _c_void_p]),
     "gcp_mesh_write": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _i32, _i32] + [ctypes.c_float] * 5 + [_c_void_p, _sz, _i64, _i64]
                        + [_c_void_p] * 4),
+    # mesh cleaning and vertex normals (gcp_meshclean.hip): components (faces, F, V -> label, size, status or NULL; ws, ws_bytes),
+    # select (faces, F, V, keep_largest, min_faces, ws, ws_bytes -> host int64[2] V', F'), compact (faces, F, V, vertices, colours or
+    # NULL, normals or NULL, ws, ws_bytes, V', F' -> vertices, faces, colours or NULL, normals or NULL), normals (vertices, faces, V, F
+    # -> normals; ws, ws_bytes); stream last
+    "gcp_mesh_components_workspace_bytes": (_sz, [_i64, _i64]),
+    "gcp_mesh_components": (ctypes.c_int, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _sz, _c_void_p]),
+    "gcp_mesh_clean_workspace_bytes": (_sz, [_i64, _i64]),
+    "gcp_mesh_select": (ctypes.c_int, [_c_void_p, _i64, _i64, _i64, _i64, _c_void_p, _sz, ctypes.POINTER(_i64), _c_void_p]),
+    "gcp_mesh_compact": (ctypes.c_int, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _sz, _i64, _i64] + [_c_void_p] * 5),
+    "gcp_mesh_vertex_normals_workspace_bytes": (_sz, [_i64, _i64]),
+    "gcp_mesh_vertex_normals": (ctypes.c_int, [_c_void_p, _c_void_p, _i64, _i64, _c_void_p, _c_void_p, _sz, _c_void_p]),
     # exact k nearest neighbours inside one cloud (gcp_knn.hip): xyz, n, k -> index i32[n,k], dist2 f32[n,k]; ws, ws_bytes, stream
     "gcp_knn_workspace_bytes": (_sz, [_i64]),
     "gcp_knn": (ctypes.c_int, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _sz, _c_void_p]),

@@ -11,7 +11,7 @@ the fused loss (loss.py: `splat_loss`), the optimiser step (optim.py: `HipAdam`)
 (density.py: `accumulate_screen_grads`), the 3-D smoothing filter (filter3d.py: `sampling_rate`, `filter_from_rate`,
 `apply_filter`), the lens distortion of the photographs (lens.py: `Lens`, `lens_from_colmap`, `fit_pinhole`, `undistort`) and the
 normals (normals.py: `gaussian_normals`, `normal_consistency`, `normal_consistency_map`, `depth_normals`, `median_as_depth`) and the mesh extraction
-(mesh.py: `TSDFVolume`, `extract_surface`) and the exact nearest neighbours for the initial scales (knn.py: `nearest_neighbours`,
+(mesh.py: `TSDFVolume`, `extract_surface`, `face_components`, `clean_mesh`, `vertex_normals`) and the exact nearest neighbours for the initial scales (knn.py: `nearest_neighbours`,
 `neighbour_scale`).
 Differences from the reference's class, all deliberate (those of the projection: projection.py):
   * images are permuted to (B, 3, H, W); the reference `reshape`s (H, W, 3) memory into (3, H, W), scrambling
@@ -36,7 +36,7 @@ from .filter3d import apply_filter, filter_from_rate, sampling_rate
 from .knn import nearest_neighbours, neighbour_scale
 from .lens import Lens, fit_pinhole, lens_from_colmap, undistort
 from .loss import ImageMetrics, apply_exposure, image_metrics, psnr_from_mse, splat_loss
-from .mesh import TSDFVolume, extract_surface
+from .mesh import TSDFVolume, clean_mesh, extract_surface, face_components, vertex_normals
 from .normals import depth_normals, gaussian_normals, median_as_depth, normal_consistency, normal_consistency_map
 from .optim import HipAdam
 from .projection import CENTRES, SH_FRAMES, _box_clamp, camera_inputs, splat_options  # noqa: F401  (re-exported)
@@ -57,8 +57,10 @@ __all__ = [
     "apply_exposure",
     "apply_filter",
     "camera_inputs",
+    "clean_mesh",
     "depth_normals",
     "extract_surface",
+    "face_components",
     "filter_from_rate",
     "fit_pinhole",
     "gather_metrics",
@@ -77,6 +79,7 @@ __all__ = [
     "splat_loss",
     "split_cameras",
     "undistort",
+    "vertex_normals",
 ]
 
 
@@ -808,7 +811,7 @@ class GS_model_with_param(torch.nn.Module):
     # ---- mesh extraction (mesh.py, csrc/gcp_tsdf.hip) ---------------------------------------------------------------------------
     @torch.no_grad()
     def extract_mesh(self, P, K, wh, resolution=256, bounds=None, trunc=None, alpha_min=0.5, depth_max=None, batch_size=4, colour=True,
-                     depth="expected"):
+                     depth="expected", keep_largest=None, min_faces=None, normals=False):
         """A triangle mesh of the scene -> (vertices float32 (V, 3), faces int32 (F, 3), colours float32 (V, 3) or None): the
         depth maps of the cameras (P, K, wh) — pass the TRAINING cameras — fused into a truncated signed distance volume
         (`TSDFVolume.integrate`), its zero level set extracted by marching tetrahedra (`TSDFVolume.extract`); what 2DGS, GOF,
@@ -828,9 +831,14 @@ class GS_model_with_param(torch.nn.Module):
         through 1/2, which lies on a surface at an occlusion edge and behind a faint floater, where the mean lies between the
         surfaces (2DGS's depth_ratio = 1 for bounded scenes: a pointer, not a tuned choice).  `alpha_min` gates on the real alpha
         either way.
-        A bounded scene only: no mesh cleaning, no vertex normals.
+        `keep_largest`, `min_faces`: both None (the default): the mesh as extracted, floaters included.  If either is given the
+        other defaults to 50 and `clean_mesh` drops the small connected components (2DGS's post_process_mesh rule; 50 / 50 are
+        its values: pointers, not tuned here).  `normals=True` appends a fourth element, `vertex_normals` of the mesh that is
+        returned — computed AFTER the cleaning — pointing out of the surface, towards the cameras.
+        A bounded scene only; no decimation, smoothing or hole filling.
         Nothing of the training state is touched: no `.grad`, no densification statistic, no optimiser state, no generator —
-        like `evaluate`.  The host reads are those of the projection and the binning, and one for the mesh's size.  GPU only."""
+        like `evaluate`.  The host reads are those of the projection and the binning, one for the mesh's size and, with cleaning,
+        one for the cleaned mesh's size.  GPU only."""
         n_cam, dev = P.shape[0], self.mean.device
         if depth not in ("expected", "median"):
             raise RuntimeError(f'depth: "expected" or "median", got {depth!r}')
@@ -880,4 +888,10 @@ class GS_model_with_param(torch.nn.Module):
                 depth, alpha = median_as_depth(rest[0], alpha)
             volume.integrate(depth[:, None, 1:, 1:], alpha[:, None, 1:, 1:], Pb.to(dev), Kb.to(dev),
                              image=image[:, 1:, 1:, :].permute(0, 3, 1, 2) if colour else None, alpha_min=alpha_min, depth_max=depth_max)
-        return volume.extract()
+        vertices, faces, colours = volume.extract()
+        if keep_largest is not None or min_faces is not None:
+            vertices, faces, colours, _ = clean_mesh(vertices, faces, colours, keep_largest=50 if keep_largest is None else keep_largest,
+                                                     min_faces=50 if min_faces is None else min_faces)
+        if normals:
+            return vertices, faces, colours, vertex_normals(vertices, faces)
+        return vertices, faces, colours

@@ -1,6 +1,9 @@
 """A triangle mesh out of rendered depth maps, on the HIP library (csrc/gcp_tsdf.hip): `TSDFVolume` fuses depth / alpha
 (/ colour) maps into a truncated signed distance volume, `extract_surface` takes the level set of any such volume out as an
 indexed mesh by marching tetrahedra.  The float64 statements both are tested against: tests/mesh_ref.py.  GPU tensors only.
+`face_components`, `clean_mesh` and `vertex_normals` (csrc/gcp_meshclean.hip) finish the mesh: connected components, 2DGS's
+keep-the-largest-clusters rule with an order-preserving compaction, area-weighted vertex normals; their integer / float64
+statements: tests/mesh_clean_ref.py.
 `GS_model_with_param.extract_mesh` drives them from a trained model; `ply_io.save_mesh` writes the result."""
 import ctypes
 
@@ -8,7 +11,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["TSDFVolume", "extract_surface"]
+__all__ = ["TSDFVolume", "clean_mesh", "extract_surface", "face_components", "vertex_normals"]
 
 
 def _stream(device):
@@ -78,6 +81,121 @@ def extract_surface(tsdf, weight=None, rgb=None, origin=(0.0, 0.0, 0.0), voxel=1
                                       faces.data_ptr() if n_face else None, None if (c is None or not n_vert) else colours.data_ptr(),
                                       _stream(dev)), "gcp_mesh_write")
     return vertices, faces, colours
+
+
+# ---- cleaning and normals (csrc/gcp_meshclean.hip) -----------------------------------------------------------------------------
+def _faces(faces, what):
+    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
+        raise RuntimeError(f"{what} expects faces (F, 3)")
+    if not faces.is_cuda:
+        raise RuntimeError(f"{what} is a HIP kernel: tensors must live on the GPU (no CPU path)")
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"{what}: faces must be int32 (what extract_surface returns), got {faces.dtype}")
+    return faces.detach().contiguous()
+
+
+def _rows(t, n, device, name, what):
+    if t is None:
+        return None
+    if not (torch.is_tensor(t) and tuple(t.shape) == (n, 3) and t.device == device):
+        raise RuntimeError(f"{what}: {name} ({n}, 3) on {device} expected, or None")
+    return t.detach().contiguous().float()
+
+
+def _mesh_sizes(n_vertices, n_faces, what):
+    if n_vertices < 0 or 3 * n_vertices >= 2 ** 31 or 3 * n_faces >= 2 ** 31:
+        raise RuntimeError(f"{what}: 3 V and 3 F must fit int32, got V = {n_vertices}, F = {n_faces}")
+
+
+def face_components(faces, n_vertices):
+    """The connected components of an indexed triangle list -> (label int32 (V,), size int32 (V,)), on the HIP library
+    (csrc/gcp_meshclean.hip; include/grouped_cumprod_hip.h pins every rule).  faces (F, 3) int32 on the GPU over `n_vertices`
+    vertices: any triangle list — unreferenced vertices, repeated faces, faces naming a vertex twice, ids in any order.
+    The rule: two vertices belong together when a face names both (shared VERTEX; Open3D's cluster_connected_triangles joins
+    over a shared edge — the same thing on a manifold such as `extract_surface`'s).  label[v]: the smallest vertex index of v's
+    component; size: at a component's label the number of its faces, 0 in every other row.
+    The order: none to choose — both outputs are functions of the mesh alone, the same bits on every run (a lock-free union-find
+    that always hooks the larger root under the smaller; integer atomics for the counts).
+    A face with an index outside [0, V) is never addressed through; here it is ignored.  No host read: capturable."""
+    f = _faces(faces, "face_components")
+    n_vertices, n_faces, dev = int(n_vertices), f.shape[0], f.device
+    _mesh_sizes(n_vertices, n_faces, "face_components")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        label = torch.empty(n_vertices, dtype=torch.int32, device=dev)
+        size = torch.empty(n_vertices, dtype=torch.int32, device=dev)
+        ws = torch.empty(lib.gcp_mesh_components_workspace_bytes(n_vertices, n_faces), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gcp_mesh_components(f.data_ptr() if n_faces else None, n_faces, n_vertices, label.data_ptr() if n_vertices else None,
+                                           size.data_ptr() if n_vertices else None, None, ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "gcp_mesh_components")
+    return label, size
+
+
+def vertex_normals(vertices, faces):
+    """Area-weighted vertex normals -> (V, 3) float32: Open3D's compute_vertex_normals on the HIP library
+    (csrc/gcp_meshclean.hip).  vertices (V, 3) float32, faces (F, 3) int32, on the GPU.
+    The rule: n_v = normalise(sum of (b - a) x (c - a) over the corners that name v, (a, b, c) the corner's face) — cross
+    products are not normalised, so large faces weigh more and zero-area faces nothing; a zero or non-finite sum gives
+    (0, 0, 0), never a NaN.  `extract_surface`'s faces are counter-clockwise seen from where the field grows: these normals point
+    out of the surface, towards the cameras.
+    The order: the corners are stably sorted by vertex and each vertex adds its faces in ascending corner index 3 f + j, in
+    float32, nothing fused, no atomics: the same bits on every run.  A face with an index outside [0, V) is left out.
+    No host read: capturable."""
+    f = _faces(faces, "vertex_normals")
+    if not (torch.is_tensor(vertices) and vertices.dim() == 2 and vertices.shape[1] == 3 and vertices.device == f.device):
+        raise RuntimeError(f"vertex_normals expects vertices (V, 3) on {f.device}")
+    v = vertices.detach().contiguous().float()
+    n_vertices, n_faces, dev = v.shape[0], f.shape[0], f.device
+    _mesh_sizes(n_vertices, n_faces, "vertex_normals")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        normals = torch.empty(n_vertices, 3, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.gcp_mesh_vertex_normals_workspace_bytes(n_vertices, n_faces), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gcp_mesh_vertex_normals(v.data_ptr() if n_vertices else None, f.data_ptr() if n_faces else None, n_vertices, n_faces,
+                                               normals.data_ptr() if n_vertices else None, ws.data_ptr() if ws.numel() else None, ws.numel(),
+                                               _stream(dev)), "gcp_mesh_vertex_normals")
+    return normals
+
+
+def clean_mesh(vertices, faces, colours=None, normals=None, keep_largest=50, min_faces=50):
+    """Drop the small connected components of a mesh -> (vertices, faces, colours or None, normals or None): what 2DGS, GOF,
+    RaDe-GS and PGSR do with Open3D's post_process_mesh(cluster_to_keep=50) after the fusion, on the HIP library
+    (csrc/gcp_meshclean.hip).  vertices (V, 3) float32, faces (F, 3) int32, colours / normals (V, 3) float32 or None, on the GPU.
+    The rule, 2DGS's: with c_k the `keep_largest`-th largest face count of the components of `face_components` (the smallest
+    count if there are fewer) and T = max(c_k, min_faces), a component stays iff it has at least T faces.  Ties at the threshold
+    all stay: no tie-break, a function of the mesh alone.  A vertex no kept face names is dropped — unreferenced input vertices
+    too.  50 / 50 are 2DGS's values: pointers, not tuned here.
+    The order: vertices and faces keep their input order (`extract_surface`'s: by (owner, kind) and by (cell, tetrahedron,
+    triangle)); kept rows are bit copies, faces are renumbered; with everything kept the outputs equal the inputs bit for bit.
+    Components, a sort of the counts, keep flags, two prefix sums, ONE host read of the two totals (and a status word) to size
+    the outputs, write: NOT capturable.  A face index outside [0, V) is never addressed through and raises from that read."""
+    f = _faces(faces, "clean_mesh")
+    if not (torch.is_tensor(vertices) and vertices.dim() == 2 and vertices.shape[1] == 3 and vertices.device == f.device):
+        raise RuntimeError(f"clean_mesh expects vertices (V, 3) on {f.device}")
+    keep_largest, min_faces = int(keep_largest), int(min_faces)
+    if keep_largest < 1 or min_faces < 1:
+        raise RuntimeError(f"clean_mesh: keep_largest >= 1 and min_faces >= 1 expected, got {keep_largest} and {min_faces}")
+    v = vertices.detach().contiguous().float()
+    n_vertices, n_faces, dev = v.shape[0], f.shape[0], f.device
+    _mesh_sizes(n_vertices, n_faces, "clean_mesh")
+    c = _rows(colours, n_vertices, dev, "colours", "clean_mesh")
+    n = _rows(normals, n_vertices, dev, "normals", "clean_mesh")
+    lib = _lib.load()
+    totals = (ctypes.c_int64 * 2)()
+    ptr = lambda t, rows: t.data_ptr() if (t is not None and rows) else None  # noqa: E731
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.gcp_mesh_clean_workspace_bytes(n_vertices, n_faces), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gcp_mesh_select(ptr(f, n_faces), n_faces, n_vertices, keep_largest, min_faces, ws.data_ptr(), ws.numel(), totals,
+                                       _stream(dev)), "gcp_mesh_select")
+        kept_v, kept_f = int(totals[0]), int(totals[1])
+        v_out = torch.empty(kept_v, 3, dtype=torch.float32, device=dev)
+        f_out = torch.empty(kept_f, 3, dtype=torch.int32, device=dev)
+        c_out = None if c is None else torch.empty(kept_v, 3, dtype=torch.float32, device=dev)
+        n_out = None if n is None else torch.empty(kept_v, 3, dtype=torch.float32, device=dev)
+        _lib.check(lib.gcp_mesh_compact(ptr(f, n_faces), n_faces, n_vertices, ptr(v, n_vertices), ptr(c, n_vertices), ptr(n, n_vertices),
+                                        ws.data_ptr(), ws.numel(), kept_v, kept_f, ptr(v_out, kept_v), ptr(f_out, kept_f), ptr(c_out, kept_v),
+                                        ptr(n_out, kept_v), _stream(dev)), "gcp_mesh_compact")
+    return v_out, f_out, c_out, n_out
 
 
 class TSDFVolume:

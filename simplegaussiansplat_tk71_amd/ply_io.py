@@ -136,31 +136,40 @@ def load_ply(path, device="cpu", convention="3dgs"):
 
 
 # ---- triangle meshes (mesh.py) -------------------------------------------------------------------------------------------------
-def _mesh_header(n_vert, n_face, coloured):
+def _mesh_header(n_vert, n_face, coloured, with_normals=False):
     return ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {n_vert}\n" + "property float x\nproperty float y\nproperty float z\n"
+            + ("property float nx\nproperty float ny\nproperty float nz\n" if with_normals else "")
             + ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if coloured else "")
             + f"element face {n_face}\n" + "property list uchar int vertex_indices\nend_header\n")
 
 
-def _mesh_dtypes(coloured):
-    vertex = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else [])
+def _mesh_dtypes(coloured, with_normals=False):
+    vertex = ([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if with_normals else [])
+              + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else []))
     return np.dtype(vertex), np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
-def save_mesh(path, vertices, faces, colours=None):
+def save_mesh(path, vertices, faces, colours=None, normals=None):
     """Write an indexed triangle mesh (mesh.extract_surface's outputs) as a binary little-endian .ply that MeshLab, Blender and
-    Open3D read: vertex `x y z` float, plus `red green blue` uchar when `colours` (V, 3) in [0, 1] is given (clamped, scaled by
-    255 and rounded); face `property list uchar int vertex_indices`, three indices each.  vertices (V, 3), faces (F, 3) with
-    indices in [0, V); tensors or arrays; V = 0 or F = 0 is a valid (empty) file."""
+    Open3D read: vertex `x y z` float, plus `nx ny nz` float when `normals` (V, 3) is given (mesh.vertex_normals'; between z
+    and red, where those programs look for them), plus `red green blue` uchar when `colours` (V, 3) in [0, 1] is given (clamped,
+    scaled by 255 and rounded); face `property list uchar int vertex_indices`, three indices each.  vertices (V, 3), faces (F, 3)
+    with indices in [0, V); tensors or arrays; V = 0 or F = 0 is a valid (empty) file.  Without normals the file is byte for byte
+    what it was before normals existed."""
     as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)  # noqa: E731
     v, f = as_np(vertices), as_np(faces)
     if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
         raise ValueError(f"vertices (V, 3) and faces (F, 3) expected, got {v.shape} and {f.shape}")
     if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
         raise ValueError("faces: an index outside [0, V)")
-    vertex_t, face_t = _mesh_dtypes(colours is not None)
+    vertex_t, face_t = _mesh_dtypes(colours is not None, normals is not None)
     rows = np.zeros(v.shape[0], dtype=vertex_t)
     rows["x"], rows["y"], rows["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = as_np(normals)
+        if n.shape != v.shape:
+            raise ValueError(f"normals: {v.shape} expected, got {n.shape}")
+        rows["nx"], rows["ny"], rows["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colours is not None:
         c = as_np(colours)
         if c.shape != v.shape:
@@ -170,14 +179,16 @@ def save_mesh(path, vertices, faces, colours=None):
     tris = np.zeros(f.shape[0], dtype=face_t)
     tris["n"], tris["v"] = 3, f
     with open(path, "wb") as out:
-        out.write(_mesh_header(v.shape[0], f.shape[0], colours is not None).encode("ascii"))
+        out.write(_mesh_header(v.shape[0], f.shape[0], colours is not None, normals is not None).encode("ascii"))
         out.write(rows.tobytes())
         out.write(tris.tobytes())
 
 
-def load_mesh(path, device="cpu"):
+def load_mesh(path, device="cpu", with_normals=False):
     """-> (vertices float32 (V, 3), faces int32 (F, 3), colours float32 (V, 3) in [0, 1] or None) on `device`: the inverse of
-    save_mesh (colours come back as multiples of 1 / 255).  Reads the layout save_mesh writes and nothing else."""
+    save_mesh (colours come back as multiples of 1 / 255).  with_normals=True: a fourth element, the stored normals float32
+    (V, 3), or None if the file has none; by default stored normals are ignored.  Reads the layouts save_mesh writes and
+    nothing else."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header\n")
@@ -189,13 +200,13 @@ def load_mesh(path, device="cpu"):
     if [e[0] for e in elements] != ["vertex", "face"]:
         raise ValueError("a vertex element followed by a face element expected")
     (_, n_vert), (_, n_face) = elements
-    for coloured in (False, True):
-        if header == _mesh_header(n_vert, n_face, coloured):
+    for coloured, has_normals in ((False, False), (True, False), (False, True), (True, True)):
+        if header == _mesh_header(n_vert, n_face, coloured, has_normals):
             break
     else:
-        raise ValueError(f"{path}: not the mesh layout save_mesh writes (binary little-endian; x y z float [red green blue uchar]; "
-                         "list uchar int vertex_indices)")
-    vertex_t, face_t = _mesh_dtypes(coloured)
+        raise ValueError(f"{path}: not the mesh layout save_mesh writes (binary little-endian; x y z float [nx ny nz float] "
+                         "[red green blue uchar]; list uchar int vertex_indices)")
+    vertex_t, face_t = _mesh_dtypes(coloured, has_normals)
     if len(body) != n_vert * vertex_t.itemsize + n_face * face_t.itemsize:
         raise ValueError(f"{path}: {n_vert} vertices and {n_face} faces expected, the file's length does not match")
     rows = np.frombuffer(body, dtype=vertex_t, count=n_vert)
@@ -206,4 +217,8 @@ def load_mesh(path, device="cpu"):
     c = np.stack([rows["red"], rows["green"], rows["blue"]], axis=1).astype(np.float32) / np.float32(255.0) if coloured else None
     faces = np.zeros((n_face, 3), dtype=np.int32)
     faces[:] = tris["v"]
-    return (torch.from_numpy(v).to(device), torch.from_numpy(faces).to(device), None if c is None else torch.from_numpy(c).to(device))
+    out = (torch.from_numpy(v).to(device), torch.from_numpy(faces).to(device), None if c is None else torch.from_numpy(c).to(device))
+    if not with_normals:
+        return out
+    n = np.stack([rows["nx"], rows["ny"], rows["nz"]], axis=1).astype(np.float32) if has_normals else None
+    return out + (None if n is None else torch.from_numpy(n).to(device),)
